@@ -9,14 +9,18 @@ A "step" = one full PTrainer.run_step in the mutual-learning phase (BASELINE.jso
 teacher forward on B unlabelled weak views, student supervised forward on 2B labelled views, student unsupervised
 forward on B strong views, ONE backward, gradient all-reduce (RCCL) for N>1, clip + SGD.  Per GPU B_label =
 B_unlabel = --per-gpu-batch (weak scaling: per-GPU work fixed).  img/s = N*(B_label+B_unlabel)/step_seconds
-(SURVEY.md 8d).  Synthetic uint8 images resident in HBM before the timed region, random-init weights, fp32.
+(SURVEY.md 8d).  Synthetic uint8 images resident in HBM before the timed region, random-init weights, fp32; the inputs
+(images, boxes, resize ratios, initial weights) are seeded, identical from run to run for the same arguments.
 
-Prints ONE JSON line (rank 0) with `roofline` (MFMA conv kernel, HIP-event timed inside the timed region) and,
-at N=1, `cpu_baseline` (the CPU oracle on the host cores, bounded sample)."""
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step`, ...).  --full adds everything else: `roofline` and `kernels` (MFMA conv kernel, HIP-event timed inside the
+timed region, traffic from rocprofv3 PMC passes), at N=1 `cpu_baseline` (the CPU oracle on the host cores, bounded sample)
+and the extra legs, and at N>1 the data-parallel self-check.  --dump-outputs DIR writes what the last timed step produced."""
 import argparse
 import json
 import math
 import os
+import random
 import sys
 import time
 
@@ -146,7 +150,7 @@ def extra_leg(flags, steps=20, warmup=5, pmc="auto"):
     """One more leg of the SAME script in a fresh process, after the headline's timed region (so that nothing of it perturbs the
     fp32 number): returns the leg's own JSON line reduced to what the headline line carries for it, or {"error": ...}."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--full",
            "--no-cpu-baseline", "--no-extras", "--pmc-traffic", pmc] + flags
     try:
         r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -162,6 +166,31 @@ def extra_leg(flags, steps=20, warmup=5, pmc="auto"):
                                             "algorithmic_bytes_per_launch", "kernel", "avg_launch_ms", "calls",
                                             "effective_direct_tflops")},
             "kernels": d["kernels"], "losses": d["losses"], "command": " ".join(["python", "bench.py"] + cmd[2:])}
+
+
+DUMP_SAMPLE = 1 << 20       # positions drawn from each flat buffer for --dump-outputs (4 MB of float32 per file)
+
+
+def dump_outputs(out_dir, trainer):
+    """--dump-outputs: what the last timed run_step produced.  Its return value, the metrics dict (every loss term,
+    total_loss, grad_norm; not the host-side data_time), as 0-d float64 arrays <key>.npy; and what it left in the flat
+    buffers, as float32 samples at fixed, seeded positions: student_params.npy and teacher_params.npy (same positions,
+    same layout) and student_grad.npy.  12 MB in all."""
+    import numpy as np
+
+    def sample(t, seed):
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+            t = t[idx.to(t.device)]
+        return t.float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in trainer.last_metrics.items():
+        if k != "data_time":
+            np.save(os.path.join(out_dir, f"{k}.npy"), np.asarray(v, dtype=np.float64))
+    np.save(os.path.join(out_dir, "student_params.npy"), sample(trainer.student.flat, 1))
+    np.save(os.path.join(out_dir, "teacher_params.npy"), sample(trainer.teacher.flat, 1))
+    np.save(os.path.join(out_dir, "student_grad.npy"), sample(trainer.student.grad, 2))
 
 
 def main():
@@ -188,18 +217,26 @@ def main():
     ap.add_argument("--grad-reduce", default="all_reduce", choices=["all_reduce", "reduce_scatter"],
                     help="N > 1: the bucketed gradient exchange as all-reduce or as reduce-scatter + all-gather (engine/flat.py)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1 default run only: skip the two extra legs that the JSON line carries next to the fp32 headline -- "
-                         "`amp` (the same workload with SOLVER.AMP.ENABLED, BASELINE configs[4]'s precision) and `student_only` "
-                         "(BASELINE configs[1], batch 8)")
+                    help="N = 1 --full run only: skip the extra legs that the JSON line carries next to the fp32 headline -- "
+                         "`amp` (the same workload with SOLVER.AMP.ENABLED, BASELINE configs[4]'s precision), `student_only` "
+                         "(BASELINE configs[1], batch 8) and `sustained`")
     ap.add_argument("--tile-schedule", default=None, choices=["static", "dynamic"],
                     help="tile schedule of the persistent F(4x4,3x3) kernel (default: PTrainer's choice -- static on one GPU, dynamic "
                          "work queues when the gradient exchange is active; csrc/wino4.hip)")
     ap.add_argument("--batches", type=int, default=2,
                     help="distinct synthetic batches resident in HBM, rotated over the steps (the `sustained` leg uses 4)")
     ap.add_argument("--pmc-traffic", default="auto", choices=["auto", "off"],
-                    help="auto (N = 1): measure roofline.traffic after the timed region by re-running one step under rocprofv3 "
-                         "PMC passes; off: report the committed profile's number, labelled as such")
+                    help="--full only. auto (N = 1): measure roofline.traffic after the timed region by re-running one step under "
+                         "rocprofv3 PMC passes; off: report the committed profile's number, labelled as such")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: HIP-event timing of every launch group inside the timed region "
+                         "(`roofline`, `kernels`, `step_conv_tflops`), roofline traffic under rocprofv3 (--pmc-traffic), the CPU "
+                         "baseline (N = 1), the extra legs (N = 1) and the data-parallel self-check (`distributed`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step produced as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config3:
         args.per_gpu_batch = 8
 
@@ -227,7 +264,10 @@ def main():
         "SOLVER.AMP.ENABLED", bool(args.amp)])
     K = cfg.MODEL.ROI_HEADS.NUM_CLASSES
     torch.manual_seed(0)                                                # identical init on all ranks
-    trainer = PTrainer(cfg, grad_reduce=args.grad_reduce)
+    # resize()'s shrink ratios from a seeded generator of the bench's own (PTrainer's default draws from the unseeded global
+    # `random`, same distribution): the same arguments give the same inputs from run to run
+    ratio_rng = random.Random(4321 + rank)
+    trainer = PTrainer(cfg, grad_reduce=args.grad_reduce, ratio_fn=lambda: ratio_rng.uniform(0.5, 1.0))
     if args.tile_schedule:
         ops.set_tile_schedule(args.tile_schedule)
     gen = torch.Generator().manual_seed(1234 + rank * 1000)
@@ -253,7 +293,8 @@ def main():
     for i in range(args.warmup):
         trainer.run_step(batches[i % NB])
     sync()
-    ops.profile_start()
+    if args.full:
+        ops.profile_start()
     ms0 = torch.cuda.memory_stats()
     t0 = time.perf_counter()
     step_ms, early = [], []
@@ -269,24 +310,27 @@ def main():
         print(f"[bench] per-step ms {[round(v, 1) for v in step_ms]}; device mallocs in the timed region: "
               f"{ms1.get('num_device_alloc', 0) - ms0.get('num_device_alloc', 0)}, reserved "
               f"{ms1.get('reserved_bytes.all.current', 0) / 2**30:.1f} GiB", file=sys.stderr)
-    prof = ops.profile_stop()
+    prof = ops.profile_stop() if args.full else None
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt_max = float(t.item())
-    # self-verification of the data-parallel run (all ranks take part): what the process group really looks like, every
-    # rank's own step time, and that the replicas are still bit-identical after the timed steps
-    from probabilisticteacher_amd.engine.flat import replicas_identical
-    per_rank = torch.tensor([dt / args.steps * 1e3], dtype=torch.float64, device=dev)
-    if world > 1:
-        gathered = [torch.empty_like(per_rank) for _ in range(world)]
-        dist.all_gather(gathered, per_rank)
-        per_rank_ms = [float(g.item()) for g in gathered]
-    else:
-        per_rank_ms = [float(per_rank.item())]
-    same_s, sums_s = replicas_identical(trainer.student.flat)
-    same_t, _ = replicas_identical(trainer.teacher.flat)
-    assert same_s and same_t, f"data-parallel replicas diverged: student checksums {sums_s}"
+    if args.full:
+        # self-verification of the data-parallel run (all ranks take part): what the process group really looks like, every
+        # rank's own step time, and that the replicas are still bit-identical after the timed steps
+        from probabilisticteacher_amd.engine.flat import replicas_identical
+        per_rank = torch.tensor([dt / args.steps * 1e3], dtype=torch.float64, device=dev)
+        if world > 1:
+            gathered = [torch.empty_like(per_rank) for _ in range(world)]
+            dist.all_gather(gathered, per_rank)
+            per_rank_ms = [float(g.item()) for g in gathered]
+        else:
+            per_rank_ms = [float(per_rank.item())]
+        same_s, sums_s = replicas_identical(trainer.student.flat)
+        same_t, _ = replicas_identical(trainer.teacher.flat)
+        assert same_s and same_t, f"data-parallel replicas diverged: student checksums {sums_s}"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer)
     dt = dt_max
 
     if rank == 0:
@@ -294,19 +338,6 @@ def main():
         value = world * 2 * B * args.steps / dt             # burn-in step: label_q + label_k = 2B images as well
         srt = sorted(step_ms)
         median = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])
-        traffic, traffic_src = (measured_pmc_traffic(args) if args.pmc_traffic == "auto" and world == 1
-                                else (None, "not measured in this run (--pmc-traffic off or N > 1)"))
-        if traffic is None and not args.amp:
-            fb, fb_src = committed_pmc_traffic()
-            traffic, traffic_src = fb, f"{fb_src}; {traffic_src}"
-        peak = PEAK_BF16_MFMA_TFLOPS if args.amp else PEAK_F32_MFMA_TFLOPS
-        # the dominant kernel: the fused Winograd F(2x2,3x3) kernel (fp32 bench) / the bf16-storage direct kernel (--amp).
-        # `achieved` / `frac` price the MFMA FLOPs the kernel ISSUES (never above the peak); the direct-convolution FLOPs the
-        # same launches stand for are reported next to it as `effective_direct_tflops`
-        dom = "p8_conv3x3" if args.amp else "conv3x3_wino4"
-        conv = prof.get(dom, {"ms": 0.0, "flops": 0.0, "issued": 0.0, "bytes": 0.0, "calls": 0})
-        ach = conv["issued"] / (conv["ms"] * 1e-3) / 1e12 if conv["ms"] > 0 else 0.0
-        eff = conv["flops"] / (conv["ms"] * 1e-3) / 1e12 if conv["ms"] > 0 else 0.0
         out = {
             "metric": ("student-only train-step img/s at 1333x800" if args.student_only else
                        "teacher-student train-step img/s at 1333x800") +
@@ -323,44 +354,59 @@ def main():
                                     f"BASELINE configs[{'3' if args.config3 else '2'}]: final_c2f.yaml (K=8) full teacher+student+EMA step, per-GPU "
                                     f"{B} labelled + {B} unlabelled synthetic {W}x{H} images, BURN_UP_STEP=0, random init"),
                        "global_batch": 2 * B * world, "parallelism": f"dp{world}"},
-            "roofline": {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
-                         "frac": ach / peak, "traffic": traffic,
-                         "traffic_unit": "HBM-side bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE)",
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": conv["bytes"] / max(conv["calls"], 1),
-                         "kernel": ("p8_conv3x3_kernel<MT> (bf16 storage: all 3x3 conv fwd + dgrad launches)" if args.amp else
-                                    "conv3x3_wino4p_kernel (fused Winograd F(4x4,3x3), positions split over the wave pair, round 6: every 3x3 conv fwd + dgrad launch with "
-                                    ">= 64 input channels; the 3-channel stem runs conv3x3_stem_kernel, listed under kernels)"),
-                         "achieved_is": "MFMA FLOPs issued by the kernel (36 multiplies per 4x4 tile and channel pair -- a quarter of "
-                                        "the direct algorithm's 144 -- tile padding included) / HIP-event time; equals the direct "
-                                        "FLOPs for the bf16 kernels.  effective_direct_tflops prices the same launches by the direct "
-                                        "convolution's FLOPs (SURVEY 8d's per-image figure)",
-                         "effective_direct_tflops": eff,
-                         "effective_direct_over_peak": eff / peak,
-                         "calls": conv["calls"],
-                         "avg_launch_ms": conv["ms"] / max(conv["calls"], 1),
-                         "mfma_flops_issued_per_launch_avg": conv["issued"] / max(conv["calls"], 1),
-                         "direct_flops_per_launch_avg": conv["flops"] / max(conv["calls"], 1)},
-            "kernels": {k: {"ms_per_step": v["ms"] / args.steps, "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12)
-                            if v["ms"] > 0 and v["flops"] else None, "calls_per_step": v["calls"] / args.steps}
-                        for k, v in prof.items()},
-            "step_conv_tflops": ((0.67106 + 0.90253) if args.student_only else 2.696) * 2 * B * world * args.steps / dt
-            if (H, W) == (800, 1333) else None,
-            "losses": {k: v for k, v in trainer.last_metrics.items() if k.startswith("loss")},
-            "distributed": {"world_size_seen_by_process_group": dist.get_world_size() if dist.is_initialized() else 1,
-                            "backend": dist.get_backend() if dist.is_initialized() else None,
-                            "per_rank_ms_per_step": per_rank_ms,
-                            "grad_exchange": {"mode": trainer.reducer.mode, "active": trainer.reducer.active,
-                                              "buckets": len(trainer.reducer.buckets),
-                                              "buckets_launched_during_backward_avg": sum(early) / max(len(early), 1),
-                                              "overlap_fraction": (sum(early) / max(len(early), 1)) / len(trainer.reducer.buckets),
-                                              "bytes_exchanged_per_step": trainer.reducer.bytes_per_step if trainer.reducer.active else 0},
-                            "replicas_bit_identical_after_run": bool(same_s and same_t),
-                            "student_checksums": [str(v) for v in sums_s]},
         }
-        if world == 1 and not args.no_cpu_baseline and not args.amp:
+        if args.full:
+            traffic, traffic_src = (measured_pmc_traffic(args) if args.pmc_traffic == "auto" and world == 1
+                                    else (None, "not measured in this run (--pmc-traffic off or N > 1)"))
+            if traffic is None and not args.amp:
+                fb, fb_src = committed_pmc_traffic()
+                traffic, traffic_src = fb, f"{fb_src}; {traffic_src}"
+            peak = PEAK_BF16_MFMA_TFLOPS if args.amp else PEAK_F32_MFMA_TFLOPS
+            # the dominant kernel: the fused Winograd F(2x2,3x3) kernel (fp32 bench) / the bf16-storage direct kernel (--amp).
+            # `achieved` / `frac` price the MFMA FLOPs the kernel ISSUES (never above the peak); the direct-convolution FLOPs the
+            # same launches stand for are reported next to it as `effective_direct_tflops`
+            dom = "p8_conv3x3" if args.amp else "conv3x3_wino4"
+            conv = prof.get(dom, {"ms": 0.0, "flops": 0.0, "issued": 0.0, "bytes": 0.0, "calls": 0})
+            ach = conv["issued"] / (conv["ms"] * 1e-3) / 1e12 if conv["ms"] > 0 else 0.0
+            eff = conv["flops"] / (conv["ms"] * 1e-3) / 1e12 if conv["ms"] > 0 else 0.0
+            out["roofline"] = {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
+                               "frac": ach / peak, "traffic": traffic,
+                               "traffic_unit": "HBM-side bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE)",
+                               "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": conv["bytes"] / max(conv["calls"], 1),
+                               "kernel": ("p8_conv3x3_kernel<MT> (bf16 storage: all 3x3 conv fwd + dgrad launches)" if args.amp else
+                                          "conv3x3_wino4p_kernel (fused Winograd F(4x4,3x3), positions split over the wave pair, round 6: every 3x3 conv fwd + dgrad launch with "
+                                          ">= 64 input channels; the 3-channel stem runs conv3x3_stem_kernel, listed under kernels)"),
+                               "achieved_is": "MFMA FLOPs issued by the kernel (36 multiplies per 4x4 tile and channel pair -- a quarter of "
+                                              "the direct algorithm's 144 -- tile padding included) / HIP-event time; equals the direct "
+                                              "FLOPs for the bf16 kernels.  effective_direct_tflops prices the same launches by the direct "
+                                              "convolution's FLOPs (SURVEY 8d's per-image figure)",
+                               "effective_direct_tflops": eff,
+                               "effective_direct_over_peak": eff / peak,
+                               "calls": conv["calls"],
+                               "avg_launch_ms": conv["ms"] / max(conv["calls"], 1),
+                               "mfma_flops_issued_per_launch_avg": conv["issued"] / max(conv["calls"], 1),
+                               "direct_flops_per_launch_avg": conv["flops"] / max(conv["calls"], 1)}
+            out["kernels"] = {k: {"ms_per_step": v["ms"] / args.steps, "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12)
+                                  if v["ms"] > 0 and v["flops"] else None, "calls_per_step": v["calls"] / args.steps}
+                              for k, v in prof.items()}
+            out["step_conv_tflops"] = (((0.67106 + 0.90253) if args.student_only else 2.696) * 2 * B * world * args.steps / dt
+                                       if (H, W) == (800, 1333) else None)
+        out["losses"] = {k: v for k, v in trainer.last_metrics.items() if k.startswith("loss")}
+        if args.full:
+            out["distributed"] = {"world_size_seen_by_process_group": dist.get_world_size() if dist.is_initialized() else 1,
+                                  "backend": dist.get_backend() if dist.is_initialized() else None,
+                                  "per_rank_ms_per_step": per_rank_ms,
+                                  "grad_exchange": {"mode": trainer.reducer.mode, "active": trainer.reducer.active,
+                                                    "buckets": len(trainer.reducer.buckets),
+                                                    "buckets_launched_during_backward_avg": sum(early) / max(len(early), 1),
+                                                    "overlap_fraction": (sum(early) / max(len(early), 1)) / len(trainer.reducer.buckets),
+                                                    "bytes_exchanged_per_step": trainer.reducer.bytes_per_step if trainer.reducer.active else 0},
+                                  "replicas_bit_identical_after_run": bool(same_s and same_t),
+                                  "student_checksums": [str(v) for v in sums_s]}
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.amp:
             out["cpu_baseline"] = cpu_baseline(H, W, K, student_only=args.student_only)
-        if world == 1 and not args.no_extras and not args.amp and not args.student_only and not args.config3:
+        if args.full and world == 1 and not args.no_extras and not args.amp and not args.student_only and not args.config3:
             # BASELINE configs[4]'s precision and configs[1] on the driver's record: the same PTrainer workload with
             # SOLVER.AMP.ENABLED (pt/engine/trainer.py:98), and the student-only burn-in step at batch 8 -- each in its own
             # process after the fp32 timed region; the headline keys above stay fp32

@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY.  Nothing under ``probabilisticteacher_amd/`` may import
 this package; only ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baseline``
-leg of ``bench.py`` use it, and only as the checker (never as the thing measured
+leg of ``bench.py --full`` use it, and only as the checker (never as the thing measured
 or shipped).
 
 Layout
