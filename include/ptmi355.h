@@ -457,6 +457,20 @@ int ptmi_rpn_soft_obj_loss(const float* t, const float* x, int64_t k, int c, flo
 int ptmi_kl_efl_loss(const float* q, const float* mu_p, const float* slog_p, const uint8_t* fg,
                      int64_t rows, float tau, float lambda, int efl, int reduction, float inv_norm,
                      float* loss_out, float* dq, float* dmu_p, float* ws, ptmi_stream_t s);
+/* UNSUPNET.MODEL_TYPE = LAPLACE counterpart of ptmi_gaussian_nll_sum (same arguments and layouts):
+ * box_regression.py:38-40,177-183 / fast_rcnn.py:298-307: sum over rows of
+ * -log(exp(-|mu-t|/sqrt(var+1e-9)) / sqrt(4(var+0.3)) + 1e-9) * inv_norm, var = sigmoid(slog). */
+int ptmi_laplace_nll_sum(const float* d, const float* t, int64_t rows, float inv_norm,
+                         float* loss_out, float* dd, float* dt, float* ws, ptmi_stream_t s);
+/* UNSUPNET.MODEL_TYPE = LAPLACE counterpart of ptmi_kl_efl_loss (same arguments, selection and
+ * reductions): rpn.py:319-344 / fast_rcnn.py:238-257, per coordinate with vp = var_p*tau,
+ * KL = sqrt(vp) exp(-|mu_q-mu_p|/sqrt(vp))/sqrt(var_q) + |mu_q-mu_p|/sqrt(var_q)
+ *      + 0.5 log(var_q/vp) - 1,
+ * entropy-focal weight (1 - (1 + 0.5 log(4 var_p)) / (1 + log 2))^lambda (unclamped). */
+int ptmi_laplace_kl_efl_loss(const float* q, const float* mu_p, const float* slog_p,
+                             const uint8_t* fg, int64_t rows, float tau, float lambda, int efl,
+                             int reduction, float inv_norm, float* loss_out, float* dq,
+                             float* dmu_p, float* ws, ptmi_stream_t s);
 /* backward of get_deltas w.r.t. the SOURCE boxes (anchors), accumulated into danchors (na,4):
  * rows index anchors via anchor_index[i] (int64).  Used only for the differentiable anchors
  * (rpn.py:311 with danchor=True, anchor_generator.py:147). */

@@ -11,6 +11,8 @@
 //   soft_ce_efl         fast_rcnn.py:179-213
 //   rpn_soft_obj_loss   rpn.py:285-304  (keeps the sigmoid(1-x) quirk of :299)
 //   kl_efl_loss         rpn.py:321-355, fast_rcnn.py:215-263
+//   laplace_nll_sum     box_regression.py:38-40,177-183; fast_rcnn.py:298-307       (UNSUPNET.MODEL_TYPE = LAPLACE)
+//   laplace_kl_efl_loss rpn.py:319-344, fast_rcnn.py:238-257                         (UNSUPNET.MODEL_TYPE = LAPLACE)
 #include "common.h"
 
 namespace {
@@ -294,6 +296,88 @@ __global__ __launch_bounds__(256) void kl_efl_kernel(const float* __restrict__ q
     }
 }
 
+// ------------------------------------------------------------------------------------------ Laplace (UNSUPNET.MODEL_TYPE = LAPLACE)
+// The gradients are those of the reference expressions as written (+1e-9 terms included); sign(0) = 0, what torch's abs
+// backward gives.
+__device__ __forceinline__ float signf_(float x) { return (float)((x > 0.f) - (x < 0.f)); }
+
+// -log(laplace_dist_pdf(mu; t, var) + 1e-9), var = sigmoid(slog)   (box_regression.py:38-40; row layout of gnll_kernel)
+__global__ __launch_bounds__(256) void lnll_kernel(const float* __restrict__ d, const float* __restrict__ tg,
+                                                   int64_t rows, float inv_norm, float* __restrict__ dd,
+                                                   float* __restrict__ dt, float* __restrict__ ws)
+{
+    __shared__ float sm[4];
+    float acc = 0.f;
+    const int64_t total = rows * 4;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i >> 2;
+        const int c = (int)(i & 3);
+        const float mu = d[r * 8 + c], sl = d[r * 8 + 4 + c], t = tg[i];
+        const float var = sigmoidf_(sl);
+        const float diff = mu - t;
+        const float ad = fabsf(diff);
+        const float a = sqrtf(var + 1e-9f);
+        const float pdf = expf(-ad / a) / sqrtf(4.0f * (var + 0.3f));
+        acc += -logf(pdf + 1e-9f);
+        const float gp = -1.f / (pdf + 1e-9f) * pdf;                     // dL/dpdf * pdf
+        const float gmu = gp * (-signf_(diff) / a) * inv_norm;
+        dd[r * 8 + c] = gmu;
+        dd[r * 8 + 4 + c] = gp * (ad / (2.f * a * a * a) - 1.f / (2.f * (var + 0.3f))) * var * (1.f - var) * inv_norm;
+        if (dt) dt[i] = -gmu;
+    }
+    const float t = block_sum_256(acc, sm);
+    if (threadIdx.x == 0) ws[WS_SUM + blockIdx.x] = t;
+}
+
+// Laplace KL(p || q) with the Laplace entropy-focal weight (rpn.py:319-344, fast_rcnn.py:238-257); selection, reduction and
+// gscale exactly as kl_efl_kernel.  The entropy base is not clamped (neither the reference nor kl_efl_kernel clamps it).
+__global__ __launch_bounds__(256) void lkl_efl_kernel(const float* __restrict__ q, const float* __restrict__ mup,
+                                                      const float* __restrict__ slp, const uint8_t* __restrict__ fg,
+                                                      int64_t rows, float tau, float lambda, int efl, float gscale,
+                                                      float* __restrict__ dq, float* __restrict__ dmup,
+                                                      float* __restrict__ ws)
+{
+    __shared__ float sm[4];
+    float acc = 0.f, cnt = 0.f;
+    const int64_t total = rows * 4;
+    const float max_ent = 1.f + logf(2.f);
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i >> 2;
+        const int c = (int)(i & 3);
+        float gmu = 0.f, gsl = 0.f;
+        if (!fg || fg[r]) {
+            const float var_p0 = sigmoidf_(slp[i]);
+            float w = 1.f;
+            if (efl) {
+                const float ent = 1.f + 0.5f * logf(4.f * var_p0);
+                w = powf(1.f - ent / max_ent, lambda);
+            }
+            const float var_p = var_p0 * tau;
+            const float var_q = sigmoidf_(q[r * 8 + 4 + c]);
+            const float rp = sqrtf(var_p), rq = sqrtf(var_q);
+            const float diff = q[r * 8 + c] - mup[i];
+            const float ad = fabsf(diff);
+            const float E = expf(-ad / rp);
+            const float kl = rp * E / rq + ad / rq + 0.5f * logf(var_q / var_p) - 1.f;
+            acc += kl * w;
+            if (c == 0) cnt += 1.f;
+            gmu = w * signf_(diff) * (1.f - E) / rq * gscale;
+            const float rq3 = rq * rq * rq;
+            const float dvq = w * (-0.5f * rp * E / rq3 - 0.5f * ad / rq3 + 0.5f / var_q);
+            gsl = dvq * var_q * (1.f - var_q) * gscale;
+        }
+        dq[r * 8 + c] = gmu;
+        dq[r * 8 + 4 + c] = gsl;
+        if (dmup) dmup[i] = -gmu;
+    }
+    const float t = block_sum_256(acc, sm);
+    const float tc = block_sum_256(cnt, sm);
+    if (threadIdx.x == 0) {
+        ws[WS_SUM + blockIdx.x] = t;
+        ws[WS_CNT + blockIdx.x] = tc;
+    }
+}
+
 int finalize(float* ws, int nb, float scale, int mean_mode, float* loss_out, hipStream_t st, const char* name)
 {
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, st, ws, nb, scale, mean_mode, loss_out, ws + WS_SCALE);
@@ -413,6 +497,50 @@ int ptmi_kl_efl_loss(const float* q, const float* mu_p, const float* slog_p, con
             hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for(rows * 4)), dim3(256), 0, st, dmu_p, rows * 4,
                                ws + WS_SCALE);
             PTMI_LAUNCH_CHECK("kl_scale_mu");
+        }
+    }
+    return 0;
+}
+
+int ptmi_laplace_nll_sum(const float* d, const float* t, int64_t rows, float inv_norm, float* loss_out, float* dd,
+                         float* dt, float* ws, ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(loss_out && ws && rows >= 0, "laplace_nll_sum: bad args");
+    hipStream_t st = (hipStream_t)s;
+    const int nb = blocks_for(rows * 4);
+    if (rows > 0) {
+        PTMI_CHECK_ARG(d && t && dd, "laplace_nll_sum: null buffer");
+        hipLaunchKernelGGL(lnll_kernel, dim3(nb), dim3(256), 0, st, d, t, rows, inv_norm, dd, dt, ws);
+        PTMI_LAUNCH_CHECK("laplace_nll_sum");
+    }
+    return finalize(ws, rows > 0 ? nb : 0, inv_norm, 0, loss_out, st, "lnll_finalize");
+}
+
+int ptmi_laplace_kl_efl_loss(const float* q, const float* mu_p, const float* slog_p, const uint8_t* fg, int64_t rows,
+                             float tau, float lambda, int efl, int reduction, float inv_norm, float* loss_out, float* dq,
+                             float* dmu_p, float* ws, ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(loss_out && ws && rows >= 0 && (reduction == 0 || reduction == 1), "laplace_kl_efl_loss: bad args");
+    hipStream_t st = (hipStream_t)s;
+    const int nb = blocks_for(rows * 4);
+    if (rows > 0) {
+        PTMI_CHECK_ARG(q && mu_p && slog_p && dq, "laplace_kl_efl_loss: null buffer");
+        hipLaunchKernelGGL(lkl_efl_kernel, dim3(nb), dim3(256), 0, st, q, mu_p, slog_p, fg, rows, tau, lambda, efl,
+                           reduction == 0 ? inv_norm : 1.0f, dq, dmu_p, ws);
+        PTMI_LAUNCH_CHECK("laplace_kl_efl_loss");
+    } else {
+        hipError_t e = hipMemsetAsync(ws, 0, sizeof(float) * 2049, st);
+        if (e != hipSuccess) { ptmi_set_error("laplace_kl_efl_loss: memset failed"); return -2; }
+    }
+    const int rc = finalize(ws, rows > 0 ? nb : 0, inv_norm, reduction, loss_out, st, "lkl_finalize");
+    if (rc) return rc;
+    if (reduction == 1 && rows > 0) {
+        hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for(rows * 8)), dim3(256), 0, st, dq, rows * 8, ws + WS_SCALE);
+        PTMI_LAUNCH_CHECK("lkl_scale");
+        if (dmu_p) {
+            hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for(rows * 4)), dim3(256), 0, st, dmu_p, rows * 4,
+                               ws + WS_SCALE);
+            PTMI_LAUNCH_CHECK("lkl_scale_mu");
         }
     }
     return 0;

@@ -14,7 +14,7 @@ from torch import nn
 from .. import ops
 from ..registry import ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY
 from ..structures import Boxes, FreeInstances
-from .box_regression import Box2BoxTransform
+from .box_regression import Box2BoxTransform, uncertainty_losses
 from . import sampling
 
 GT_LOGIT = math.log((1.0 - 1e-10) / (1 - (1.0 - 1e-10)))     # proposal_utils.py:207
@@ -119,6 +119,7 @@ class GuassianFastRCNNOutputLayers(nn.Module):
         self.num_classes = cfg.MODEL.ROI_HEADS.NUM_CLASSES
         assert not cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG
         self.model_type = cfg.UNSUPNET.MODEL_TYPE
+        self.nll_loss, self.kl_loss = uncertainty_losses(self.model_type)        # fast_rcnn.py:286-307, :238-257
         self.box2box_transform = Box2BoxTransform(weights=cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS)
         self.cls_score = _LinearP(input_size, self.num_classes + 1)
         self.bbox_pred = _LinearP(input_size, self.num_classes * 8)
@@ -144,7 +145,7 @@ class GuassianFastRCNNOutputLayers(nn.Module):
         fg = torch.nonzero((gt_classes >= 0) & (gt_classes < K)).squeeze(1)
         d = deltas.view(-1, K, 8)[fg, gt_classes[fg]]
         tgt = self.box2box_transform.get_deltas(pb[fg], gb[fg])
-        loss_box = ops.gaussian_nll_sum(d, tgt, 1.0 / max(gt_classes.numel(), 1.0))
+        loss_box = self.nll_loss(d, tgt, 1.0 / max(gt_classes.numel(), 1.0))
         out = {"loss_cls": loss_cls, "loss_box_reg": loss_box}
         return {k: v * self.loss_weight.get(k, 1.0) for k, v in out.items()}
 
@@ -166,7 +167,7 @@ class GuassianFastRCNNOutputLayers(nn.Module):
                 mu_p = self.box2box_transform.get_deltas(pb[rows], psb[rows])
                 sig_sel = sig_p[rows].contiguous()
             q = deltas.view(-1, K, 8)[rows, cls[rows]]                 # one gather instead of the per-row loop (:159-161)
-            out["loss_box_reg"] = ops.kl_efl_loss(q, mu_p, sig_sel, None, U.TAU[1], U.EFL_LAMBDA[1], bool(U.EFL), 1, 1.0)
+            out["loss_box_reg"] = self.kl_loss(q, mu_p, sig_sel, None, U.TAU[1], U.EFL_LAMBDA[1], bool(U.EFL), 1, 1.0)
         return out
 
     # ---- teacher inference (fast_rcnn.py:338-409, :34-141)

@@ -17,7 +17,7 @@ from .. import ops
 from ..registry import PROPOSAL_GENERATOR_REGISTRY, RPN_HEAD_REGISTRY
 from ..structures import Boxes, FreeInstances
 from .anchor_generator import build_anchor_generator
-from .box_regression import Box2BoxTransform
+from .box_regression import Box2BoxTransform, uncertainty_losses
 from . import sampling
 
 
@@ -129,6 +129,7 @@ class GuassianRPN(nn.Module):
         self.min_box_size = float(cfg.MODEL.PROPOSAL_GENERATOR.MIN_SIZE)
         self.anchor_boundary_thresh = R.BOUNDARY_THRESH
         self.loss_weight = {"loss_rpn_cls": R.LOSS_WEIGHT, "loss_rpn_loc": R.BBOX_REG_LOSS_WEIGHT * R.LOSS_WEIGHT}
+        self.nll_loss, self.kl_loss = uncertainty_losses(cfg.UNSUPNET.MODEL_TYPE)     # box_regression.py:177-183, rpn.py:319-344
 
     def head_outputs(self, feats):
         """the head's outputs in the flat anchor-order layout when the head offers it (no permute copies), else D2's"""
@@ -210,7 +211,7 @@ class GuassianRPN(nn.Module):
         d_rows = d8.reshape(-1, 8)[flat_pos]
         a_rows = anchors[flat_pos % r]
         tgt = self.box2box_transform.get_deltas(a_rows, gt_rows)
-        loss_loc = ops.gaussian_nll_sum(d_rows, tgt, inv)
+        loss_loc = self.nll_loss(d_rows, tgt, inv)
         return {"loss_rpn_cls": loss_cls, "loss_rpn_loc": loss_loc}
 
     # ------------------------------------------------------------------ unsupervised (rpn.py:257-361, 426-430)
@@ -240,8 +241,7 @@ class GuassianRPN(nn.Module):
         if has_box:
             q = d8.reshape(-1, 8)[flat]
             mu_p = self.box2box_transform.get_deltas(anchors[flat % r], tgt_all)
-            out["loss_rpn_loc"] = ops.kl_efl_loss(q, mu_p, sig_all, fg, U.TAU[1], U.EFL_LAMBDA[1],
-                                                  bool(U.EFL), 0, inv)
+            out["loss_rpn_loc"] = self.kl_loss(q, mu_p, sig_all, fg, U.TAU[1], U.EFL_LAMBDA[1], bool(U.EFL), 0, inv)
         return out
 
 

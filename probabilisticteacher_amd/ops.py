@@ -1106,20 +1106,25 @@ def bce_logits_sum(logits, labels_i8, inv_norm):
     return _BCELogitsSum.apply(logits, labels_i8, inv_norm)
 
 
+def _nll_sum_forward(ctx, entry: str, d, t, inv_norm: float):
+    """forward of the box-regression NLL Functions: `entry` = ptmi_gaussian_nll_sum | ptmi_laplace_nll_sum (same arguments)"""
+    d = _chk(d.contiguous())
+    t = _chk(t.contiguous())
+    rows = d.shape[0]
+    loss = torch.empty(1, dtype=F32, device=d.device)
+    dd = torch.empty_like(d)
+    dt = torch.empty_like(t) if ctx.needs_input_grad[1] else None
+    _lib.call(entry, _ptr(d), _ptr(t), rows, float(inv_norm), _ptr(loss), _ptr(dd), _ptr(dt),
+              _ptr(_loss_ws(d.device)), _stream())
+    ctx.has_dt = dt is not None
+    ctx.save_for_backward(dd, dt) if dt is not None else ctx.save_for_backward(dd)
+    return loss.reshape(())
+
+
 class _GaussianNLLSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, d, t, inv_norm: float):
-        d = _chk(d.contiguous())
-        t = _chk(t.contiguous())
-        rows = d.shape[0]
-        loss = torch.empty(1, dtype=F32, device=d.device)
-        dd = torch.empty_like(d)
-        dt = torch.empty_like(t) if ctx.needs_input_grad[1] else None
-        _lib.call("ptmi_gaussian_nll_sum", _ptr(d), _ptr(t), rows, float(inv_norm), _ptr(loss), _ptr(dd), _ptr(dt),
-                  _ptr(_loss_ws(d.device)), _stream())
-        ctx.has_dt = dt is not None
-        ctx.save_for_backward(dd, dt) if dt is not None else ctx.save_for_backward(dd)
-        return loss.reshape(())
+        return _nll_sum_forward(ctx, "ptmi_gaussian_nll_sum", d, t, inv_norm)
 
     @staticmethod
     def backward(ctx, g):
@@ -1132,6 +1137,18 @@ class _GaussianNLLSum(torch.autograd.Function):
 
 def gaussian_nll_sum(d, t, inv_norm):
     return _GaussianNLLSum.apply(d, t, inv_norm)
+
+
+class _LaplaceNLLSum(_GaussianNLLSum):
+    """UNSUPNET.MODEL_TYPE = LAPLACE: -log(laplace_dist_pdf + 1e-9) summed (ptmi_laplace_nll_sum); backward as the Gaussian's"""
+
+    @staticmethod
+    def forward(ctx, d, t, inv_norm: float):
+        return _nll_sum_forward(ctx, "ptmi_laplace_nll_sum", d, t, inv_norm)
+
+
+def laplace_nll_sum(d, t, inv_norm):
+    return _LaplaceNLLSum.apply(d, t, inv_norm)
 
 
 class _SoftmaxCEMean(torch.autograd.Function):
@@ -1212,24 +1229,29 @@ def rpn_soft_obj_loss(teacher, x, tau, lam, efl, inv_norm):
     return _RPNSoftObj.apply(teacher, x, tau, lam, efl, inv_norm)
 
 
+def _kl_efl_forward(ctx, entry: str, q, mu_p, slog_p, fg, tau, lam, efl, reduction, inv_norm):
+    """forward of the KL + entropy-weight Functions: `entry` = ptmi_kl_efl_loss | ptmi_laplace_kl_efl_loss (same arguments)"""
+    q = _chk(q.contiguous())
+    mu_p = _chk(mu_p.contiguous())
+    slog_p = _chk(slog_p.contiguous())
+    if fg is not None:
+        fg = _chk(fg.contiguous(), torch.uint8)
+    rows = q.shape[0]
+    loss = torch.empty(1, dtype=F32, device=q.device)
+    dq = torch.empty_like(q)
+    dmu = torch.empty_like(mu_p) if ctx.needs_input_grad[1] else None
+    _lib.call(entry, _ptr(q), _ptr(mu_p), _ptr(slog_p), _ptr(fg), rows, float(tau), float(lam),
+              int(efl), int(reduction), float(inv_norm), _ptr(loss), _ptr(dq), _ptr(dmu),
+              _ptr(_loss_ws(q.device)), _stream())
+    ctx.has_dmu = dmu is not None
+    ctx.save_for_backward(dq, dmu) if dmu is not None else ctx.save_for_backward(dq)
+    return loss.reshape(())
+
+
 class _KLEFL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, mu_p, slog_p, fg, tau, lam, efl, reduction, inv_norm):
-        q = _chk(q.contiguous())
-        mu_p = _chk(mu_p.contiguous())
-        slog_p = _chk(slog_p.contiguous())
-        if fg is not None:
-            fg = _chk(fg.contiguous(), torch.uint8)
-        rows = q.shape[0]
-        loss = torch.empty(1, dtype=F32, device=q.device)
-        dq = torch.empty_like(q)
-        dmu = torch.empty_like(mu_p) if ctx.needs_input_grad[1] else None
-        _lib.call("ptmi_kl_efl_loss", _ptr(q), _ptr(mu_p), _ptr(slog_p), _ptr(fg), rows, float(tau), float(lam),
-                  int(efl), int(reduction), float(inv_norm), _ptr(loss), _ptr(dq), _ptr(dmu),
-                  _ptr(_loss_ws(q.device)), _stream())
-        ctx.has_dmu = dmu is not None
-        ctx.save_for_backward(dq, dmu) if dmu is not None else ctx.save_for_backward(dq)
-        return loss.reshape(())
+        return _kl_efl_forward(ctx, "ptmi_kl_efl_loss", q, mu_p, slog_p, fg, tau, lam, efl, reduction, inv_norm)
 
     @staticmethod
     def backward(ctx, g):
@@ -1242,6 +1264,19 @@ class _KLEFL(torch.autograd.Function):
 
 def kl_efl_loss(q, mu_p, slog_p, fg, tau, lam, efl, reduction, inv_norm):
     return _KLEFL.apply(q, mu_p, slog_p, fg, tau, lam, efl, reduction, inv_norm)
+
+
+class _LaplaceKLEFL(_KLEFL):
+    """UNSUPNET.MODEL_TYPE = LAPLACE: the Laplace KL with the Laplace entropy weight (ptmi_laplace_kl_efl_loss); backward as
+    the Gaussian's"""
+
+    @staticmethod
+    def forward(ctx, q, mu_p, slog_p, fg, tau, lam, efl, reduction, inv_norm):
+        return _kl_efl_forward(ctx, "ptmi_laplace_kl_efl_loss", q, mu_p, slog_p, fg, tau, lam, efl, reduction, inv_norm)
+
+
+def laplace_kl_efl_loss(q, mu_p, slog_p, fg, tau, lam, efl, reduction, inv_norm):
+    return _LaplaceKLEFL.apply(q, mu_p, slog_p, fg, tau, lam, efl, reduction, inv_norm)
 
 
 # ============================================================================ optimiser / EMA / image prep
