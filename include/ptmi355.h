@@ -533,6 +533,19 @@ int ptmi_aug_hflip_batched(const int64_t* desc, int n, int64_t max_elems, ptmi_s
  *              p4 = output size along the pass, p5 = 0: (3,h,w) -> (3,h,p4), 1: (3,h,w) -> (3,p4,w).  A resize is the x pass
  *              followed by the y pass (a pass whose size does not change is skipped).  Down-scaling factors up to 15. */
 int ptmi_aug_resize_pass_batched(const int64_t* desc, int n, int64_t max_out_elems, ptmi_stream_t s);
+/* Windowed sources: D2 RandomCrop (INPUT.CROP) in front of the resize / flip of the weak augmentation
+ * (dataset_mapper.py:53-60) without a cropped copy.  `wdesc` is a DEVICE table of 16 int64 words per image:
+ * [src, dst, row pitch, plane pitch, x0, y0, ch, cw, p8, p9, 0 x 6] -- src = element (0,0,0) of the underlying planar uint8
+ * image (pitches in bytes), the window is rows y0 .. y0+ch-1, columns x0 .. x0+cw-1 of each of its 3 planes and must lie
+ * inside the image (the caller checks; the kernels do not know the image's size); dst is dense.  src != dst.
+ *   resize_window : the arithmetic of `resize` on the window: p8 = output size along the pass, p9 = 0: -> (3,ch,p8),
+ *              1: -> (3,p8,cw).  The filter support is clamped to the WINDOW, so the result is Pillow's resize of the
+ *              cropped array: no neighbour outside the crop contributes.  max_out_elems = max_i 3 * output pixels.
+ *   flip_window : p8 = 0 copies the window, 1 flips it left-right, 2 top-bottom (D2 RandomFlip horizontal / vertical)
+ *              -> (3,ch,cw).  max_elems = max_i 3*ch*cw.
+ * Four output bytes per thread, moved as one dword where the addresses are 4-byte aligned and as bytes where not. */
+int ptmi_aug_resize_window_pass_batched(const int64_t* wdesc, int n, int64_t max_out_elems, ptmi_stream_t s);
+int ptmi_aug_flip_window_batched(const int64_t* wdesc, int n, int64_t max_elems, ptmi_stream_t s);
 
 /* ------------------------------------------------------------------ diagnostics
  * CU-contention probe (round 6; no counterpart in the reference): n_cus workgroups that each hold one CU (64 KB of LDS: no

@@ -130,6 +130,8 @@ SIGNATURES = {
     "ptmi_aug_box_blur_batched": (_i, [_vp, _i, _i64, _vp]),
     "ptmi_aug_hflip_batched": (_i, [_vp, _i, _i64, _vp]),
     "ptmi_aug_resize_pass_batched": (_i, [_vp, _i, _i64, _vp]),
+    "ptmi_aug_resize_window_pass_batched": (_i, [_vp, _i, _i64, _vp]),
+    "ptmi_aug_flip_window_batched": (_i, [_vp, _i, _i64, _vp]),
 }
 
 _lib = None

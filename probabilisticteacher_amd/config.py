@@ -153,7 +153,8 @@ def get_cfg() -> CfgNode:
     C.SEED = -1
     C.VIS_PERIOD = 0
     C.INPUT = CfgNode(dict(FORMAT="BGR", MIN_SIZE_TRAIN=(800,), MAX_SIZE_TRAIN=1333, MIN_SIZE_TEST=800,
-                           MAX_SIZE_TEST=1333, RANDOM_FLIP="horizontal"))
+                           MAX_SIZE_TEST=1333, RANDOM_FLIP="horizontal", MIN_SIZE_TRAIN_SAMPLING="choice",
+                           CROP=CfgNode(dict(ENABLED=False, TYPE="relative_range", SIZE=[0.9, 0.9]))))       # D2 0.5 defaults
     C.DATASETS = CfgNode(dict(TRAIN=(), TEST=()))
     C.DATALOADER = CfgNode(dict(NUM_WORKERS=4, FILTER_EMPTY_ANNOTATIONS=True))      # D2 default: True
     C.TEST = CfgNode(dict(DETECTIONS_PER_IMAGE=100, EVAL_PERIOD=0))

@@ -1,4 +1,5 @@
-// augment.hip -- strong augmentation of the two-crop mapper on the device (gfx950), byte-exact with Pillow.
+// augment.hip -- weak (crop window, resize, flip) and strong augmentation of the two-crop mapper on the device (gfx950),
+// byte-exact with Pillow.
 //
 // Replaces the PIL / torchvision CPU work the reference does per image in its DataLoader workers:
 // pt/data/detection_utils.py:38-60 build_strong_augmentation [RandomApply(ColorJitter(0.4, 0.4, 0.4, 0.1), p=0.8),
@@ -216,6 +217,156 @@ __global__ __launch_bounds__(256) void aug_resize_pass_kernel(const int64_t* __r
     }
 }
 
+// ---------------------------------------------------------------- windowed sources: INPUT.CROP of the weak augmentation
+// D2 RandomCrop in front of ResizeShortestEdge / RandomFlip (dataset_mapper.py:53-60).  The crop is never materialised: the
+// first kernel that touches an image reads a WINDOW of it.  wdesc: 16 int64 words per image (include/ptmi355.h):
+//   [0] src = element (0, 0, 0) of the underlying planar image, [1] dst (dense), [2] row pitch, [3] plane pitch (bytes),
+//   [4] x0, [5] y0 (window origin), [6] ch, [7] cw (window size), [8] p8, [9] p9, [10..15] unused.
+// Both kernels hand every thread four consecutive output bytes of one row (a "quad"; the last quad of a row may be short),
+// so a wave writes 256 contiguous bytes; a quad moves as one dword where its address is 4-byte aligned and byte by byte
+// where it is not (odd window origins / widths).  The choice is the same for every quad of a row.
+enum { WD_WORDS = 16 };
+
+__device__ __forceinline__ uint32_t load_quad(const uint8_t* p, bool wide)
+{
+    if (wide) return *reinterpret_cast<const uint32_t*>(p);
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+__device__ __forceinline__ void store_quad(uint8_t* o, uint32_t v, int n)
+{
+    if (n == 4 && ((uintptr_t)o & 3) == 0) { *reinterpret_cast<uint32_t*>(o) = v; return; }
+    for (int j = 0; j < n; ++j) o[j] = (uint8_t)(v >> (8 * j));
+}
+
+// copy (p8 = 0), left-right flip (1: HFlipTransform) or top-bottom flip (2: VFlipTransform) of a window -> dense (3, ch, cw)
+__global__ __launch_bounds__(256) void aug_flip_window_kernel(const int64_t* __restrict__ desc)
+{
+    const int64_t* d = desc + WD_WORDS * (int64_t)blockIdx.y;
+    const uint8_t* src = (const uint8_t*)d[0];
+    uint8_t* dst = (uint8_t*)d[1];
+    const int64_t pitch = d[2], plane = d[3];
+    const int x0 = (int)d[4], y0 = (int)d[5], ch = (int)d[6], cw = (int)d[7], mode = (int)d[8];
+    const int qpr = (cw + 3) >> 2;                      // quads per output row
+    const int64_t total = 3ll * ch * qpr;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
+        const int ox = (int)(q % qpr) * 4;
+        const int64_t r = q / qpr;                      // output row over the three planes
+        const int oy = (int)(r % ch), c = (int)(r / ch);
+        const int n = cw - ox < 4 ? cw - ox : 4;
+        const int sy = mode == 2 ? ch - 1 - oy : oy;
+        const uint8_t* row = src + c * plane + (int64_t)(y0 + sy) * pitch + x0;
+        uint32_t v = 0;
+        if (n == 4) {
+            const uint8_t* p = mode == 1 ? row + (cw - 4 - ox) : row + ox;
+            v = load_quad(p, ((uintptr_t)p & 3) == 0);
+            if (mode == 1) v = __builtin_bswap32(v);
+        } else {
+            for (int j = 0; j < n; ++j) v |= (uint32_t)(mode == 1 ? row[cw - 1 - ox - j] : row[ox + j]) << (8 * j);
+        }
+        store_quad(dst + r * cw + ox, v, n);
+    }
+}
+
+// Pillow's precompute_coeffs() for output position xx, as aug_resize_pass_kernel evaluates it: the support [xmin, xmin + xmax)
+// is clamped to [0, inSize) -- for a window that is the WINDOW's extent, so a resized crop sees no pixel outside the crop --
+// and ww is the sum of the triangle weights over it.
+struct RsTaps { double center, ww; int xmin, xmax; };
+
+__device__ __forceinline__ RsTaps rs_taps(int xx, double scale, double support, double ss, int inSize)
+{
+    RsTaps t;
+    t.center = 0 + (xx + 0.5) * scale;
+    t.xmin = (int)(t.center - support + 0.5);
+    if (t.xmin < 0) t.xmin = 0;
+    t.xmax = (int)(t.center + support + 0.5);
+    if (t.xmax > inSize) t.xmax = inSize;
+    t.xmax -= t.xmin;
+    if (t.xmax > RS_MAX_TAPS) t.xmax = RS_MAX_TAPS;        // (rejected on the host)
+    t.ww = 0.0;
+    for (int x = 0; x < t.xmax; ++x) {
+        double u = (x + t.xmin - t.center + 0.5) * ss;
+        if (u < 0.0) u = -u;
+        t.ww += u < 1.0 ? 1.0 - u : 0.0;
+    }
+    return t;
+}
+
+__device__ __forceinline__ int rs_coeff(const RsTaps& t, int x, double ss)
+{
+    double u = (x + t.xmin - t.center + 0.5) * ss;
+    if (u < 0.0) u = -u;
+    double v = u < 1.0 ? 1.0 - u : 0.0;
+    if (t.ww != 0.0) v /= t.ww;
+    return v < 0 ? (int)(-0.5 + v * (1 << RS_PRECISION_BITS)) : (int)(0.5 + v * (1 << RS_PRECISION_BITS));
+}
+
+// clip8(acc >> RS_PRECISION_BITS) as a byte to be OR-ed into a quad.  Written as an unsigned shift of max(acc, 0): for the signed
+// shift-and-clamp form hipcc pairs two results into one v_ashr_pk_u8_i32 and ORs bytes 2 and 3 onto its result as if the
+// upper half were zero; on an MI355X stale bits showed up in byte 2 of the quad (a host build of the same code was exact).
+__device__ __forceinline__ uint32_t rs_round(int acc)
+{
+    const uint32_t u = (uint32_t)(acc < 0 ? 0 : acc) >> RS_PRECISION_BITS;
+    return u > 255u ? 255u : u;
+}
+
+// aug_resize_pass_kernel's arithmetic on a window: (ch, cw) -> (ch, p8) along x (p9 = 0) or (p8, cw) along y (p9 = 1).  In the
+// y pass the four outputs of a quad share their coefficients (one evaluation of the double expression tree per quad) and each
+// tap is one dword of the source row where that is aligned; in the x pass every output has its own coefficients and its taps
+// are consecutive source bytes that the neighbouring lanes read too.
+__global__ __launch_bounds__(256) void aug_resize_window_pass_kernel(const int64_t* __restrict__ desc)
+{
+    const int64_t* d = desc + WD_WORDS * (int64_t)blockIdx.y;
+    const uint8_t* src = (const uint8_t*)d[0];
+    uint8_t* dst = (uint8_t*)d[1];
+    const int64_t pitch = d[2], plane = d[3];
+    const int x0 = (int)d[4], y0 = (int)d[5], h = (int)d[6], w = (int)d[7], outSize = (int)d[8], vertical = (int)d[9];
+    const int inSize = vertical ? h : w;
+    const int oh = vertical ? outSize : h, ow = vertical ? w : outSize;
+    const int qpr = (ow + 3) >> 2;
+    const int64_t total = 3ll * oh * qpr;
+    double scale = (double)inSize / outSize, filterscale = scale;
+    if (filterscale < 1.0) filterscale = 1.0;
+    const double support = 1.0 * filterscale;
+    const double ss = 1.0 / filterscale;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
+        const int ox = (int)(q % qpr) * 4;
+        const int64_t r = q / qpr;
+        const int oy = (int)(r % oh), c = (int)(r / oh);
+        const int n = ow - ox < 4 ? ow - ox : 4;
+        const uint8_t* win = src + c * plane + (int64_t)y0 * pitch + x0;       // element (c, 0, 0) of the window
+        uint32_t out = 0;
+        if (vertical) {
+            const RsTaps t = rs_taps(oy, scale, support, ss, inSize);
+            const uint8_t* p = win + (int64_t)t.xmin * pitch + ox;
+            const bool wide = n == 4 && ((((uintptr_t)p) | (uintptr_t)pitch) & 3) == 0;
+            int acc[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = 1 << (RS_PRECISION_BITS - 1);
+            for (int x = 0; x < t.xmax; ++x, p += pitch) {
+                const int k = rs_coeff(t, x, ss);
+                uint32_t v = 0;
+                if (n == 4) v = load_quad(p, wide);
+                else for (int j = 0; j < n; ++j) v |= (uint32_t)p[j] << (8 * j);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] += (int)((v >> (8 * j)) & 255u) * k;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) out |= rs_round(acc[j]) << (8 * j);
+        } else {
+            const uint8_t* line = win + (int64_t)oy * pitch;
+            for (int j = 0; j < n; ++j) {
+                const RsTaps t = rs_taps(ox + j, scale, support, ss, inSize);
+                const uint8_t* p = line + t.xmin;
+                int acc = 1 << (RS_PRECISION_BITS - 1);
+                for (int x = 0; x < t.xmax; ++x) acc += (int)p[x] * rs_coeff(t, x, ss);
+                out |= rs_round(acc) << (8 * j);
+            }
+        }
+        store_quad(dst + r * ow + ox, out, n);
+    }
+}
+
 inline dim3 grid_for(int n, int64_t max_elems)
 {
     int64_t bx = (max_elems + 1023) / 1024;
@@ -275,6 +426,24 @@ int ptmi_aug_resize_pass_batched(const int64_t* desc, int n, int64_t max_out_ele
     PTMI_CHECK_ARG(desc && n > 0 && n < 65536 && max_out_elems > 0, "aug_resize_pass_batched: bad args");
     hipLaunchKernelGGL(aug_resize_pass_kernel, grid_for(n, max_out_elems), dim3(256), 0, (hipStream_t)s, desc);
     PTMI_LAUNCH_CHECK("aug_resize_pass_batched");
+    return 0;
+}
+
+int ptmi_aug_resize_window_pass_batched(const int64_t* wdesc, int n, int64_t max_out_elems, ptmi_stream_t s)
+{
+    if (n == 0) return 0;
+    PTMI_CHECK_ARG(wdesc && n > 0 && n < 65536 && max_out_elems > 0, "aug_resize_window_pass_batched: bad args");
+    hipLaunchKernelGGL(aug_resize_window_pass_kernel, grid_for(n, max_out_elems), dim3(256), 0, (hipStream_t)s, wdesc);
+    PTMI_LAUNCH_CHECK("aug_resize_window_pass_batched");
+    return 0;
+}
+
+int ptmi_aug_flip_window_batched(const int64_t* wdesc, int n, int64_t max_elems, ptmi_stream_t s)
+{
+    if (n == 0) return 0;
+    PTMI_CHECK_ARG(wdesc && n > 0 && n < 65536 && max_elems > 0, "aug_flip_window_batched: bad args");
+    hipLaunchKernelGGL(aug_flip_window_kernel, grid_for(n, max_elems), dim3(256), 0, (hipStream_t)s, wdesc);
+    PTMI_LAUNCH_CHECK("aug_flip_window_batched");
     return 0;
 }
 

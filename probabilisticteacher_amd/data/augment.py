@@ -154,11 +154,115 @@ def resize_shortest_edge_size(h: int, w: int, short_edge: int, max_size: int) ->
     return int(newh + 0.5), int(neww + 0.5)
 
 
-def resize_batch(images: Sequence[torch.Tensor], sizes: Sequence[Tuple[int, int]]) -> List[torch.Tensor]:
-    """Image.resize((new_w, new_h), Image.BILINEAR) of D2's ResizeTransform for a batch of planar uint8 images: the x pass
-    of all images in one launch, then the y pass (a pass that does not change the size is skipped, as in Pillow)."""
+CROP_TYPES = ("relative_range", "relative", "absolute", "absolute_range")
+FLIP_MODES = {"none": 0, "horizontal": 1, "vertical": 2}          # p8 of ptmi_aug_flip_window_batched
+Window = Tuple[int, int, int, int]                                 # (y0, x0, ch, cw)
+
+
+def _f32(x: float) -> float:
+    return struct.unpack("<f", struct.pack("<f", float(x)))[0]
+
+
+def crop_size(crop_type: str, size: Sequence[float], h: int, w: int, u: Optional[Sequence[float]] = None) -> Tuple[int, int]:
+    """D2 0.5 RandomCrop.get_crop_size for an (h, w) image -> (ch, cw).  `size` = INPUT.CROP.SIZE.
+    "relative": fractions of the image, rounded half up.  "relative_range": `u` = two uniform draws in [0, 1); D2 holds SIZE
+    as a float32 array, so f_i = float32(s_i) + u_i * (float32(1) - float32(s_i)) evaluated in double, then as "relative".
+    "absolute": (s0, s1) clamped to the image.  "absolute_range": `u` = the two integers drawn from
+    [min(h, s0), min(h, s1)] and [min(w, s0), min(w, s1)] (both ends inclusive; `crop_size_range`).
+    D2 asserts that the crop fits the image: a result larger than the image (relative sizes above 1) is a ValueError."""
+    s0, s1 = size
+    if crop_type == "relative":
+        ch, cw = int(h * s0 + 0.5), int(w * s1 + 0.5)
+    elif crop_type == "relative_range":
+        f0, f1 = (_f32(s) + float(ui) * _f32(1.0 - _f32(s)) for s, ui in zip((s0, s1), u))
+        ch, cw = int(h * f0 + 0.5), int(w * f1 + 0.5)
+    elif crop_type == "absolute":
+        ch, cw = min(int(s0), h), min(int(s1), w)
+    elif crop_type == "absolute_range":
+        (hlo, hhi), (wlo, whi) = crop_size_range(size, h, w)
+        ch, cw = int(u[0]), int(u[1])
+        if not (hlo <= ch <= hhi and wlo <= cw <= whi):
+            raise ValueError(f"absolute_range crop {ch}x{cw} outside [{hlo}, {hhi}] x [{wlo}, {whi}]")
+    else:
+        raise ValueError(f"Unknown crop type {crop_type!r} (INPUT.CROP.TYPE is one of {CROP_TYPES})")
+    if ch > h or cw > w or ch < 1 or cw < 1:
+        raise ValueError(f"{crop_type} crop {tuple(size)} of a {h}x{w} image gives {ch}x{cw}: the crop must fit the image")
+    return ch, cw
+
+
+def crop_size_range(size: Sequence[float], h: int, w: int) -> Tuple[Tuple[int, int], Tuple[int, int]]:
+    """the inclusive integer ranges "absolute_range" draws ch and cw from"""
+    s0, s1 = int(size[0]), int(size[1])
+    if s0 > s1:
+        raise ValueError(f"absolute_range crop needs SIZE[0] <= SIZE[1], got {tuple(size)}")
+    return (min(h, s0), min(h, s1)), (min(w, s0), min(w, s1))
+
+
+def sample_crop(crop_type: str, size: Sequence[float], h: int, w: int, rng: random.Random) -> Window:
+    """D2 RandomCrop.get_transform -> (y0, x0, ch, cw).  Draw order: u0, u1 ("relative_range") or the two integers
+    ("absolute_range"; the other types draw nothing), then y0 in [0, h - ch], then x0 in [0, w - cw]."""
+    u = None
+    if crop_type == "relative_range":
+        u = (rng.random(), rng.random())
+    elif crop_type == "absolute_range":
+        hr, wr = crop_size_range(size, h, w)
+        u = (rng.randint(*hr), rng.randint(*wr))
+    ch, cw = crop_size(crop_type, size, h, w, u)
+    y0 = rng.randint(0, h - ch)
+    x0 = rng.randint(0, w - cw)
+    return y0, x0, ch, cw
+
+
+def sample_short_edge(min_size_train: Sequence[int], sampling: str, rng: random.Random) -> int:
+    """D2 ResizeShortestEdge: "choice" picks one of the sizes, "range" a uniform integer in [min, max], both ends included"""
+    if sampling == "choice":
+        return rng.choice(min_size_train)
+    if sampling == "range":
+        if len(min_size_train) != 2:
+            raise ValueError(f"INPUT.MIN_SIZE_TRAIN_SAMPLING 'range' needs exactly two sizes, got {tuple(min_size_train)}")
+        return rng.randint(min(min_size_train), max(min_size_train))
+    raise ValueError(f"Unknown INPUT.MIN_SIZE_TRAIN_SAMPLING {sampling!r} ('choice' or 'range')")
+
+
+def _window_row(im: torch.Tensor, window: Optional[Window], dst: torch.Tensor, p8: int, p9: int) -> List[int]:
+    """one 16-word descriptor row of the windowed kernels; the kernels trust it, so the window is checked here"""
+    h, w = im.shape[-2:]
+    y0, x0, ch, cw = (0, 0, h, w) if window is None else (int(v) for v in window)
+    if not (0 <= y0 and 0 <= x0 and ch >= 1 and cw >= 1 and y0 + ch <= h and x0 + cw <= w):
+        raise ValueError(f"window (y0, x0, ch, cw) = {(y0, x0, ch, cw)} is not inside the {h}x{w} image")
+    return [im.data_ptr(), dst.data_ptr(), w, h * w, x0, y0, ch, cw, p8, p9, 0, 0, 0, 0, 0, 0]
+
+
+def flip_batch(images: Sequence[torch.Tensor], modes: Sequence[int],
+               windows: Optional[Sequence[Optional[Window]]] = None) -> List[torch.Tensor]:
+    """Copy (mode 0), D2 HFlipTransform (1) or VFlipTransform (2) of planar uint8 images, or of a window (y0, x0, ch, cw) of
+    each: a crop that needs no resize is taken here, by the launch that flips / copies anyway.  One launch for the batch."""
     if not images:
         return []
+    dev = images[0].device
+    images = [_chk(im.contiguous(), torch.uint8, "image") for im in images]
+    windows = list(windows) if windows is not None else [None] * len(images)
+    rows, out = [], []
+    for im, m, win in zip(images, modes, windows):
+        if int(m) not in (0, 1, 2):
+            raise ValueError(f"flip mode {m}: 0 copy, 1 left-right, 2 top-bottom")
+        o = torch.empty((3,) + (tuple(im.shape[-2:]) if win is None else (int(win[2]), int(win[3]))), dtype=torch.uint8, device=dev)
+        rows.append(_window_row(im, win, o, int(m), 0))
+        out.append(o)
+    _launch("ptmi_aug_flip_window_batched", rows, dev, max(o.numel() for o in out))
+    return out
+
+
+def resize_batch(images: Sequence[torch.Tensor], sizes: Sequence[Tuple[int, int]],
+                 windows: Optional[Sequence[Optional[Window]]] = None) -> List[torch.Tensor]:
+    """Image.resize((new_w, new_h), Image.BILINEAR) of D2's ResizeTransform for a batch of planar uint8 images: the x pass
+    of all images in one launch, then the y pass (a pass that does not change the size is skipped, as in Pillow).
+    windows[i] = (y0, x0, ch, cw): image i is the resize of that crop of images[i] (D2 RandomCrop before the resize).  The
+    crop is not copied out: the first pass that runs for the image reads the window in place, with the filter clamped to it."""
+    if not images:
+        return []
+    if windows is not None and any(win is not None for win in windows):
+        return _resize_windows(images, sizes, list(windows))
     dev = images[0].device
     cur = [_chk(im.contiguous(), torch.uint8, "image") for im in images]
     for vertical in (0, 1):
@@ -178,4 +282,34 @@ def resize_batch(images: Sequence[torch.Tensor], sizes: Sequence[Tuple[int, int]
             _launch("ptmi_aug_resize_pass_batched", rows, dev, max(o.numel() for o in outs))
             for i, o in zip(idx, outs):
                 cur[i] = o
+    return cur
+
+
+def _resize_windows(images, sizes, windows) -> List[torch.Tensor]:
+    """resize_batch with at least one window: every pass is one launch of the windowed kernel for the whole batch (an image
+    without a window, and the dense intermediate of a second pass, is the window that covers all of it)."""
+    dev = images[0].device
+    cur = [_chk(im.contiguous(), torch.uint8, "image") for im in images]
+    win = list(windows)
+    for vertical in (0, 1):
+        rows, outs, idx = [], [], []
+        for i, (im, (nh, nw)) in enumerate(zip(cur, sizes)):
+            h, w = im.shape[-2:] if win[i] is None else (int(win[i][2]), int(win[i][3]))
+            new = nh if vertical else nw
+            if new == (h if vertical else w):
+                continue
+            if math.ceil(max((h if vertical else w) / new, 1.0)) * 2 + 1 > 32:
+                raise ValueError(f"resize {h}x{w} -> {nh}x{nw}: down-scaling factor beyond the kernel's 32-tap window")
+            o = torch.empty((3, new, w) if vertical else (3, h, new), dtype=torch.uint8, device=dev)
+            rows.append(_window_row(im, win[i], o, new, vertical))
+            outs.append(o)
+            idx.append(i)
+        if rows:
+            _launch("ptmi_aug_resize_window_pass_batched", rows, dev, max(o.numel() for o in outs))
+            for i, o in zip(idx, outs):
+                cur[i], win[i] = o, None
+    left = [i for i, wn in enumerate(win) if wn is not None]         # a window that already has its target size: copy it out
+    if left:
+        for i, o in zip(left, flip_batch([cur[i] for i in left], [0] * len(left), [win[i] for i in left])):
+            cur[i] = o
     return cur
