@@ -309,6 +309,31 @@ int ptmi_roi_align_bwd_grouped(const float* dout, const float* rois, const int32
                                float* dfeat, void* ws, int n, int c, int h, int w, int r, int pooled,
                                float scale, ptmi_stream_t s);
 
+/* The ROIAlign variants of detectron2's ROIPooler (MODEL.ROI_BOX_HEAD.POOLER_TYPE "ROIAlign", POOLER_SAMPLING_RATIO > 0): the
+ * four entry points above followed by torchvision roi_align's `aligned` (1: half-pixel shift, "ROIAlignV2"; 0: no shift and a
+ * ROI at least one cell wide and high, "ROIAlign") and `sampling_ratio` (0: ceil(roi extent / pooled) samples a bin side;
+ * > 0: that many).  (1, 0) computes what the entry points above compute (those launch kernels compiled without the two
+ * parameters).  The ptmi_roi_align_*ws_bytes queries hold for every variant.  aligned outside {0, 1} or sampling_ratio < 0: error. */
+int ptmi_roi_align_fwd_ex(const float* feat, const float* rois, float* out, int n, int c, int h,
+                          int w, int r, int pooled, float scale, ptmi_stream_t s, int aligned, int sampling_ratio);
+int ptmi_roi_align_bwd_ex(const float* dout, const float* rois, float* dfeat, int n, int c, int h,
+                          int w, int r, int pooled, float scale, ptmi_stream_t s, int aligned, int sampling_ratio);
+int ptmi_roi_align_fwd_grouped_ex(const float* feat, const float* rois, const int32_t* img_offsets,
+                                  float* out, void* ws, int n, int c, int h, int w, int r, int pooled,
+                                  float scale, ptmi_stream_t s, int aligned, int sampling_ratio);
+int ptmi_roi_align_bwd_grouped_ex(const float* dout, const float* rois, const int32_t* img_offsets,
+                                  float* dfeat, void* ws, int n, int c, int h, int w, int r, int pooled,
+                                  float scale, ptmi_stream_t s, int aligned, int sampling_ratio);
+/* torchvision roi_pool (POOLER_TYPE "ROIPool"): out (R, c, pooled, pooled) = the maximum over the integer cells of each bin
+ * (roundf of the scaled corners, floor / ceil bin edges clamped to the map), argmax (same shape, int32) = flat index h * W + w
+ * of the first maximum in raster order, -1 (and value 0) for an empty bin.  Bit-exact against the reference loop. */
+int ptmi_roi_pool_fwd(const float* feat, const float* rois, float* out, int32_t* argmax, int n, int c, int h, int w, int r,
+                      int pooled, float scale, ptmi_stream_t s);
+/* dfeat (n, c, h, w) = scatter-add of dout through argmax.  dfeat is zeroed here (r = 0 gives zeros); hardware fp32 atomics:
+ * where several bins meet in one cell the summation order varies from run to run.  No gradient to the boxes. */
+int ptmi_roi_pool_bwd(const float* dout, const int32_t* argmax, const float* rois, float* dfeat, int n, int c, int h, int w,
+                      int r, int pooled, ptmi_stream_t s);
+
 /* ------------------------------------------------------------------ boxes (N4, N5, N9)
  * anchors: D2 DefaultAnchorGenerator / pt/modeling/anchor_generator.py:108-122: out (h*w*A,4),
  * anchor n=(y*w+x)*A+a = [x*stride,y*stride,x*stride,y*stride] + cell[a] (offset 0 folded in). */

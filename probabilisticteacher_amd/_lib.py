@@ -89,6 +89,12 @@ SIGNATURES = {
     "ptmi_roi_align_fwd_p8m_fits": (_i, [_i, _i, _i, _i]),
     "ptmi_roi_align_fwd_p8m": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "ptmi_roi_align_bwd_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    "ptmi_roi_align_fwd_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _i]),
+    "ptmi_roi_align_bwd_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _i]),
+    "ptmi_roi_align_fwd_grouped_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _i]),
+    "ptmi_roi_align_bwd_grouped_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _i]),
+    "ptmi_roi_pool_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    "ptmi_roi_pool_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ptmi_grid_anchors": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp]),
     "ptmi_apply_deltas": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i64, _f, _f, _f, _f, _f, _vp]),
     "ptmi_get_deltas": (_i, [_vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp]),

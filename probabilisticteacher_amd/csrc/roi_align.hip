@@ -1,10 +1,18 @@
-// roi_align.hip -- ROIAlign (aligned=True, sampling_ratio=0 adaptive grid) fwd/bwd for gfx950.
+// roi_align.hip -- the ROI poolers (fwd/bwd) for gfx950: ROIAlign (aligned=True, sampling_ratio=0 adaptive grid: the shipped
+// configs), its variants (aligned=False, fixed sampling grid) and ROIPool.
 //
 // Replaces torchvision roi_align, which the reference reaches through detectron2's ROIPooler built at
 // pt/modeling/roi_heads/roi_heads.py:68-73 and called at :126.  Gather-bound: the
 // 50x83x512 fp32 feature map of an image (8.5 MB) lives in L2/MALL, one workgroup per ROI walks all
 // channels with threads laid out along (c, ph, pw) so that the (R, C, 7, 7) output is written with
 // fully coalesced stores.  Backward scatters with hardware fp32 atomics (-munsafe-fp-atomics).
+//
+// Variants (MODEL.ROI_BOX_HEAD.POOLER_TYPE "ROIAlign" / POOLER_SAMPLING_RATIO > 0): all ROI geometry is in roi_geom() and in the
+// sample loops of the two table kernels.  Those take a trailing parameter pack `V... v`: EMPTY for ROIAlignV2 / ratio 0 (the same
+// signature, kernel arguments and instructions as before the variants existed), one RoiVariant otherwise.  The gather, band and
+// atomic bodies are shared.  ROIPool (max pooling over integer bins, argmax saved for the backward) is at the end of the file.
+#include <cfloat>
+
 #include "common.h"
 
 namespace {
@@ -33,6 +41,32 @@ __device__ __forceinline__ RoiGeom roi_geom(const float* __restrict__ roi, float
     return g;
 }
 
+// (aligned, sampling_ratio) of torchvision roi_align: aligned = 0 drops the half-pixel shift and keeps a ROI at least one cell wide
+// and high; sampling_ratio > 0 fixes the sampling grid of a bin (0: ceil(roi extent / P) samples a side)
+struct RoiVariant { int aligned, sampling_ratio; };
+
+__device__ __forceinline__ RoiGeom roi_geom(const float* __restrict__ roi, float scale, int P, RoiVariant v)
+{
+    RoiGeom g;
+    g.b = (int)roi[0];
+    const float off = v.aligned ? 0.5f : 0.f;
+    g.sw = roi[1] * scale - off;
+    g.sh = roi[2] * scale - off;
+    const float ew = roi[3] * scale - off, eh = roi[4] * scale - off;
+    float rw = ew - g.sw, rh = eh - g.sh;
+    if (!v.aligned) {
+        rw = fmaxf(rw, 1.0f);
+        rh = fmaxf(rh, 1.0f);
+    }
+    g.bw = rw / (float)P;
+    g.bh = rh / (float)P;
+    g.gw = v.sampling_ratio > 0 ? v.sampling_ratio : (int)ceilf(rw / (float)P);
+    g.gh = v.sampling_ratio > 0 ? v.sampling_ratio : (int)ceilf(rh / (float)P);
+    const int c = g.gh * g.gw;
+    g.count = (float)(c > 1 ? c : 1);
+    return g;
+}
+
 __device__ __forceinline__ bool bilin(float y, float x, int H, int W, int& yl, int& xl, int& yh, int& xh, float& w1,
                                       float& w2, float& w3, float& w4)
 {
@@ -48,12 +82,12 @@ __device__ __forceinline__ bool bilin(float y, float x, int H, int W, int& yl, i
     return true;
 }
 
-__global__ __launch_bounds__(256) void roi_align_fwd_kernel(const float* __restrict__ feat,
-                                                            const float* __restrict__ rois, float* __restrict__ out,
-                                                            int C, int H, int W, int P, float scale)
+template <class... V>
+__device__ __forceinline__ void roi_align_fwd_body(const float* __restrict__ feat, const float* __restrict__ rois,
+                                                   float* __restrict__ out, int C, int H, int W, int P, float scale, V... v)
 {
     const int r = blockIdx.x;
-    const RoiGeom g = roi_geom(rois + 5 * (size_t)r, scale, P);
+    const RoiGeom g = roi_geom(rois + 5 * (size_t)r, scale, P, v...);
     const int PP = P * P, total = C * PP;
     const float* fb = feat + (size_t)g.b * C * H * W;
     float* ob = out + (size_t)r * total;
@@ -76,12 +110,26 @@ __global__ __launch_bounds__(256) void roi_align_fwd_kernel(const float* __restr
     }
 }
 
-__global__ __launch_bounds__(256) void roi_align_bwd_kernel(const float* __restrict__ dout,
-                                                            const float* __restrict__ rois, float* __restrict__ dfeat,
+__global__ __launch_bounds__(256) void roi_align_fwd_kernel(const float* __restrict__ feat,
+                                                            const float* __restrict__ rois, float* __restrict__ out,
                                                             int C, int H, int W, int P, float scale)
 {
+    roi_align_fwd_body(feat, rois, out, C, H, W, P, scale);
+}
+
+__global__ __launch_bounds__(256) void roi_align_fwd_var_kernel(const float* __restrict__ feat,
+                                                                const float* __restrict__ rois, float* __restrict__ out,
+                                                                int C, int H, int W, int P, float scale, RoiVariant v)
+{
+    roi_align_fwd_body(feat, rois, out, C, H, W, P, scale, v);
+}
+
+template <class... V>
+__device__ __forceinline__ void roi_align_bwd_body(const float* __restrict__ dout, const float* __restrict__ rois,
+                                                   float* __restrict__ dfeat, int C, int H, int W, int P, float scale, V... v)
+{
     const int r = blockIdx.x;
-    const RoiGeom g = roi_geom(rois + 5 * (size_t)r, scale, P);
+    const RoiGeom g = roi_geom(rois + 5 * (size_t)r, scale, P, v...);
     const int PP = P * P, total = C * PP;
     float* fb = dfeat + (size_t)g.b * C * H * W;
     const float* ob = dout + (size_t)r * total;
@@ -106,6 +154,20 @@ __global__ __launch_bounds__(256) void roi_align_bwd_kernel(const float* __restr
     }
 }
 
+__global__ __launch_bounds__(256) void roi_align_bwd_kernel(const float* __restrict__ dout,
+                                                            const float* __restrict__ rois, float* __restrict__ dfeat,
+                                                            int C, int H, int W, int P, float scale)
+{
+    roi_align_bwd_body(dout, rois, dfeat, C, H, W, P, scale);
+}
+
+__global__ __launch_bounds__(256) void roi_align_bwd_var_kernel(const float* __restrict__ dout,
+                                                                const float* __restrict__ rois, float* __restrict__ dfeat,
+                                                                int C, int H, int W, int P, float scale, RoiVariant v)
+{
+    roi_align_bwd_body(dout, rois, dfeat, C, H, W, P, scale, v);
+}
+
 // Forward for rois grouped by image.  The samples of a bin are separable: a bin's value is
 //     (1 / count) sum_{y, x} Wy_ph[y] F[y][x] Wx_pw[x]
 // over the (at most gh + 1) x (gw + 1) feature cells its gh x gw samples touch, with Wy_ph[y] = the summed y-weights of the bin's
@@ -117,13 +179,14 @@ __global__ __launch_bounds__(256) void roi_align_bwd_kernel(const float* __restr
 // planes are loaded.  Not the torchvision summation order: equal to the plain gather kernel to fp32 rounding, not bit for bit.
 struct RoiBinHeader { int sy, sx, pad0, pad1; int ylo[8]; int xlo[8]; };      // then wy[7][TS], wx[7][TS] (floats)
 
-__global__ __launch_bounds__(64) void roi_bin_tables_kernel(const float* __restrict__ rois, void* __restrict__ ws, int H, int W,
-                                                            float scale, int TS)
+template <class... V>
+__device__ __forceinline__ void roi_bin_tables_body(const float* __restrict__ rois, void* __restrict__ ws, int H, int W, float scale,
+                                                    int TS, V... v)
 {
     extern __shared__ float tw[];                    // [14][TS]
     __shared__ int slo[14], sn[14];
     const int r = blockIdx.x, t = threadIdx.x;
-    const RoiGeom g = roi_geom(rois + 5 * (size_t)r, scale, 7);
+    const RoiGeom g = roi_geom(rois + 5 * (size_t)r, scale, 7, v...);
     for (int i = t; i < 14 * TS; i += 64) tw[i] = 0.f;
     __syncthreads();
     if (t < 14) {
@@ -141,11 +204,14 @@ __global__ __launch_bounds__(64) void roi_bin_tables_kernel(const float* __restr
             if (l >= L - 1) { h2 = l = L - 1; v = (float)l; } else h2 = l + 1;
             const float lw = v - (float)l, hw = 1.f - lw;
             if (lo0 < 0) lo0 = l;                    // samples ascend: the first valid one has the lowest cell
-            if (h2 - lo0 < TS) {
+            // (a fixed grid on an aligned box with x2 < x1 descends: no table.  The adaptive grid of such a box has no samples.)
+            const bool ascends = sizeof...(V) == 0 || l >= lo0;
+            if (ascends && h2 - lo0 < TS) {
                 wv[l - lo0] += hw;
                 wv[h2 - lo0] += lw;
                 n = h2 - lo0 + 1;
-            } else n = -(1 << 20);                   // a box many times the map: a bin spans more cells than the table holds
+            } else n = -(1 << 20);                   // a box many times the map (or a fixed grid's samples many cells apart): a bin
+                                                     // spans more cells than the table holds
         }
         slo[t] = lo0 < 0 ? 0 : lo0;
         sn[t] = n;
@@ -169,6 +235,18 @@ __global__ __launch_bounds__(64) void roi_bin_tables_kernel(const float* __restr
     for (int i = t; i < 14 * TS; i += 64) wt[i] = i < 7 * TS ? tw[i] : tw[i] * inv_count;
 }
 
+__global__ __launch_bounds__(64) void roi_bin_tables_kernel(const float* __restrict__ rois, void* __restrict__ ws, int H, int W,
+                                                            float scale, int TS)
+{
+    roi_bin_tables_body(rois, ws, H, W, scale, TS);
+}
+
+__global__ __launch_bounds__(64) void roi_bin_tables_var_kernel(const float* __restrict__ rois, void* __restrict__ ws, int H, int W,
+                                                                float scale, int TS, RoiVariant v)
+{
+    roi_bin_tables_body(rois, ws, H, W, scale, TS, v);
+}
+
 constexpr int RF2_THREADS = 1024, RF2_SLOTS = 20, RF2_CG = 4;
 constexpr int RF2_CG8 = 8;   // channel planes per workgroup where they fit (variants: tools/exp/roi_variants.sh edits a COPY of this file)
 
@@ -176,14 +254,14 @@ constexpr int RF2_CG8 = 8;   // channel planes per workgroup where they fit (var
 // box head's first Linear layer under SOLVER.AMP.ENABLED (csrc/p8gemm.hip): xk[k / 8][R][8] (k = c * 49 + bin: the forward GEMM's
 // operand) and, if xt != null, xt[r / 8][C * 49][8] (the weight gradient's operand, contraction over ROIs) -- the values a pack of
 // the fp32 tensor would hold (round to nearest even), without the fp32 tensor and the two pack passes over it.
-template <bool PACK, int NCH>
+template <bool PACK, int NCH, class... V>
 __global__ __launch_bounds__(RF2_THREADS) void roi_align_fwd_bin_kernel(const float* __restrict__ feat,
                                                                         const void* __restrict__ ws,
                                                                         const int32_t* __restrict__ img_off,
                                                                         float* __restrict__ out, int C, int H, int W,
                                                                         int CG, int TS, const float* __restrict__ rois, float scale,
                                                                         unsigned short* __restrict__ xk, unsigned short* __restrict__ xt,
-                                                                        int R)
+                                                                        int R, V... v)
 {
     extern __shared__ float smem[];
     const int HW = H * W;
@@ -219,7 +297,7 @@ __global__ __launch_bounds__(RF2_THREADS) void roi_align_fwd_bin_kernel(const fl
         };
         if (sy < 0) {
             // no table (see roi_bin_tables_kernel): the torchvision loop over the bin's samples
-            const RoiGeom g = roi_geom(rois + 5 * (size_t)r, scale, 7);
+            const RoiGeom g = roi_geom(rois + 5 * (size_t)r, scale, 7, v...);
             for (int iy = 0; iy < g.gh; ++iy) {
                 const float y = g.sh + (float)ph * g.bh + ((float)iy + .5f) * g.bh / (float)g.gh;
                 for (int ix = 0; ix < g.gw; ++ix) {
@@ -279,13 +357,14 @@ __global__ __launch_bounds__(RF2_THREADS) void roi_align_fwd_bin_kernel(const fl
 // the consumer's loads do not depend on the header; the Wx rows carry the 1 / count) are built ONCE per ROI by
 // roi_bwd_tables_kernel into a workspace.
 struct RoiBwdHeader { int y0, y1, x0, x1; float count; int pad[3]; };
-__global__ __launch_bounds__(64) void roi_bwd_tables_kernel(const float* __restrict__ rois, void* __restrict__ ws,
-                                                            int H, int W, float scale)
+template <class... V>
+__device__ __forceinline__ void roi_bwd_tables_body(const float* __restrict__ rois, void* __restrict__ ws, int H, int W, float scale,
+                                                    V... v)
 {
     extern __shared__ float tsm[];                   // Wy_abs[H][8] | Wx_abs[W][8]
     __shared__ int rng[4];
     const int r = blockIdx.x, tid = threadIdx.x;
-    const RoiGeom g = roi_geom(rois + 5 * (size_t)r, scale, 7);
+    const RoiGeom g = roi_geom(rois + 5 * (size_t)r, scale, 7, v...);
     for (int i = tid; i < (H + W) * 8; i += 64) tsm[i] = 0.f;
     if (tid < 4) rng[tid] = (tid & 1) ? -1 : (1 << 30);                    // ymin, ymax, xmin, xmax
     __syncthreads();
@@ -329,6 +408,18 @@ __global__ __launch_bounds__(64) void roi_bwd_tables_kernel(const float* __restr
     float* wt = reinterpret_cast<float*>(base + sizeof(RoiBwdHeader));
     const float inv_count = 1.f / g.count;
     for (int i = tid; i < (H + W) * 8; i += 64) wt[i] = i < H * 8 ? tsm[i] : tsm[i] * inv_count;
+}
+
+__global__ __launch_bounds__(64) void roi_bwd_tables_kernel(const float* __restrict__ rois, void* __restrict__ ws,
+                                                            int H, int W, float scale)
+{
+    roi_bwd_tables_body(rois, ws, H, W, scale);
+}
+
+__global__ __launch_bounds__(64) void roi_bwd_tables_var_kernel(const float* __restrict__ rois, void* __restrict__ ws,
+                                                                int H, int W, float scale, RoiVariant v)
+{
+    roi_bwd_tables_body(rois, ws, H, W, scale, v);
 }
 
 // The accumulation kernel (round 4; lanes laid out for the ROIs the path actually sees -- median 11 x 12 feature cells: its
@@ -492,57 +583,218 @@ static int roi_fwd_planes(int c, int h, int w, int pooled)
     return cg;
 }
 
-template <bool PACK>
+template <bool PACK, class... V>
 static int roi_fwd_grouped_launch(const float* feat, const float* rois, const int32_t* img_offsets, float* out, void* ws, int n, int c,
-                                  int h, int w, int r, float scale, unsigned short* xk, unsigned short* xt, hipStream_t st)
+                                  int h, int w, int r, float scale, unsigned short* xk, unsigned short* xt, hipStream_t st, V... v)
 {
     const int cg = roi_fwd_planes(c, h, w, 7);
     const int TS = roi_tab_stride(h, w);
-    hipLaunchKernelGGL(roi_bin_tables_kernel, dim3(r), dim3(64), (size_t)14 * TS * sizeof(float), st, rois, ws, h, w, scale, TS);
+    if constexpr (sizeof...(V) == 0)
+        hipLaunchKernelGGL(roi_bin_tables_kernel, dim3(r), dim3(64), (size_t)14 * TS * sizeof(float), st, rois, ws, h, w, scale, TS);
+    else
+        hipLaunchKernelGGL(roi_bin_tables_var_kernel, dim3(r), dim3(64), (size_t)14 * TS * sizeof(float), st, rois, ws, h, w, scale, TS,
+                           v...);
     PTMI_LAUNCH_CHECK("roi_align_tables");
-    static bool attr_set = false;
+    static bool attr_set = false;                    // (one flag per instantiation)
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)roi_align_fwd_bin_kernel<PACK, RF2_CG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)roi_align_fwd_bin_kernel<PACK, RF2_CG8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)roi_align_fwd_bin_kernel<PACK, RF2_CG, V...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)roi_align_fwd_bin_kernel<PACK, RF2_CG8, V...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
     const size_t lds = (size_t)cg * h * w * sizeof(float);
     if (cg > RF2_CG)
-        hipLaunchKernelGGL((roi_align_fwd_bin_kernel<PACK, RF2_CG8>), dim3(cdiv(c, cg), n), dim3(RF2_THREADS), lds, st, feat, ws, img_offsets,
-                           out, c, h, w, cg, TS, rois, scale, xk, xt, r);
+        hipLaunchKernelGGL((roi_align_fwd_bin_kernel<PACK, RF2_CG8, V...>), dim3(cdiv(c, cg), n), dim3(RF2_THREADS), lds, st, feat, ws, img_offsets,
+                           out, c, h, w, cg, TS, rois, scale, xk, xt, r, v...);
     else
-        hipLaunchKernelGGL((roi_align_fwd_bin_kernel<PACK, RF2_CG>), dim3(cdiv(c, cg), n), dim3(RF2_THREADS), lds, st, feat, ws, img_offsets,
-                           out, c, h, w, cg, TS, rois, scale, xk, xt, r);
+        hipLaunchKernelGGL((roi_align_fwd_bin_kernel<PACK, RF2_CG, V...>), dim3(cdiv(c, cg), n), dim3(RF2_THREADS), lds, st, feat, ws, img_offsets,
+                           out, c, h, w, cg, TS, rois, scale, xk, xt, r, v...);
     PTMI_LAUNCH_CHECK("roi_align_fwd_grouped");
     return 0;
+}
+
+template <class... V>
+static int roi_fwd_launch(const float* feat, const float* rois, float* out, int n, int c, int h, int w, int r, int pooled, float scale,
+                          hipStream_t st, V... v)
+{
+    if (r == 0) return 0;
+    PTMI_CHECK_ARG(feat && out && rois && n > 0 && c > 0 && h > 0 && w > 0 && r > 0 && pooled > 0,
+                   "roi_align_fwd: bad args");
+    if constexpr (sizeof...(V) == 0)
+        hipLaunchKernelGGL(roi_align_fwd_kernel, dim3(r), dim3(256), 0, st, feat, rois, out, c, h, w, pooled, scale);
+    else
+        hipLaunchKernelGGL(roi_align_fwd_var_kernel, dim3(r), dim3(256), 0, st, feat, rois, out, c, h, w, pooled, scale, v...);
+    PTMI_LAUNCH_CHECK("roi_align_fwd");
+    return 0;
+}
+
+template <class... V>
+static int roi_bwd_launch(const float* dout, const float* rois, float* dfeat, int n, int c, int h, int w, int r, int pooled, float scale,
+                          hipStream_t st, V... v)
+{
+    if (r == 0) return 0;
+    PTMI_CHECK_ARG(dout && dfeat && rois && n > 0 && c > 0 && h > 0 && w > 0 && r > 0 && pooled > 0,
+                   "roi_align_bwd: bad args");
+    if constexpr (sizeof...(V) == 0)
+        hipLaunchKernelGGL(roi_align_bwd_kernel, dim3(r), dim3(256), 0, st, dout, rois, dfeat, c, h, w, pooled, scale);
+    else
+        hipLaunchKernelGGL(roi_align_bwd_var_kernel, dim3(r), dim3(256), 0, st, dout, rois, dfeat, c, h, w, pooled, scale, v...);
+    PTMI_LAUNCH_CHECK("roi_align_bwd");
+    return 0;
+}
+
+template <class... V>
+static int roi_fwd_grouped(const float* feat, const float* rois, const int32_t* img_offsets, float* out, void* ws, int n, int c, int h,
+                           int w, int r, int pooled, float scale, hipStream_t st, V... v)
+{
+    if (r == 0) return 0;
+    PTMI_CHECK_ARG(feat && rois && img_offsets && out && n > 0 && c > 0 && h > 0 && w > 0 && r > 0 && pooled > 0,
+                   "roi_align_fwd_grouped: bad args");
+    if (!roi_fwd_planes(c, h, w, pooled) || !ws)
+        return roi_fwd_launch(feat, rois, out, n, c, h, w, r, pooled, scale, st, v...);
+    return roi_fwd_grouped_launch<false>(feat, rois, img_offsets, out, ws, n, c, h, w, r, scale, nullptr, nullptr, st, v...);
+}
+
+template <class... V>
+static int roi_bwd_grouped(const float* dout, const float* rois, const int32_t* img_offsets, float* dfeat, void* ws, int n, int c,
+                           int h, int w, int r, int pooled, float scale, hipStream_t st, V... v)
+{
+    PTMI_CHECK_ARG(dfeat && img_offsets && n > 0 && c > 0 && h > 0 && w > 0 && r >= 0 && pooled > 0,
+                   "roi_align_bwd_grouped: bad args");
+    const size_t plane_bytes = (size_t)h * w * sizeof(float);
+    // the band kernel: RB3_WAVES row bands (at most 32 rows each), up to four channel planes per workgroup at a pitch of
+    // 16 (mod 64) floats, two workgroups per CU if they fit, one otherwise
+    const int nb = RB3_WAVES, br = cdiv(h, nb);
+    const int pitch = ((h * w + 47) / 64) * 64 + 16;
+    const size_t strips = (size_t)nb * (64 * 4 + 4 * 52) * sizeof(float);
+    int cg = (int)((80 * 1024 - strips) / ((size_t)pitch * 4));
+    if (cg < 1) cg = (int)((160 * 1024 - strips) / ((size_t)pitch * 4));
+    if (cg > RB3_PLANES) cg = RB3_PLANES;
+    if (cg > c) cg = c;
+    const bool band_ok = pooled == 7 && ws && br <= 32 && cg >= 1;
+    if (!band_ok || r == 0) {             // not the hot-path shape (or no ROI at all): zero + atomic scatter kernel
+        hipError_t e = hipMemsetAsync(dfeat, 0, (size_t)n * c * plane_bytes, st);
+        if (e != hipSuccess) { ptmi_set_error("roi_align_bwd_grouped: memset failed"); return -2; }
+        return r == 0 ? 0 : roi_bwd_launch(dout, rois, dfeat, n, c, h, w, r, pooled, scale, st, v...);
+    }
+    PTMI_CHECK_ARG(dout && rois, "roi_align_bwd_grouped: null buffer");
+    if constexpr (sizeof...(V) == 0)
+        hipLaunchKernelGGL(roi_bwd_tables_kernel, dim3(r), dim3(64), (size_t)(h + w) * 8 * sizeof(float), st, rois, ws, h, w, scale);
+    else
+        hipLaunchKernelGGL(roi_bwd_tables_var_kernel, dim3(r), dim3(64), (size_t)(h + w) * 8 * sizeof(float), st, rois, ws, h, w, scale,
+                           v...);
+    PTMI_LAUNCH_CHECK("roi_align_bwd_tables");
+    static bool attr3 = false;
+    if (!attr3) {
+        (void)hipFuncSetAttribute((const void*)roi_align_bwd_band_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr3 = true;
+    }
+    hipLaunchKernelGGL(roi_align_bwd_band_kernel, dim3(cdiv(c, cg), n), dim3(64 * nb), (size_t)cg * pitch * 4 + strips, st, dout, ws,
+                       img_offsets, dfeat, c, h, w, cg, pitch, br);
+    PTMI_LAUNCH_CHECK("roi_align_bwd_grouped(band)");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ ROIPool
+// torchvision roi_pool (detectron2 POOLER_TYPE "ROIPool"): the maximum over the integer cells of a bin.  One workgroup per ROI;
+// the bin rows' and columns' [start, end) are computed once per ROI into LDS (not once per channel), then threads run along
+// (c, ph, pw) like roi_align_fwd_kernel: the (R, C, P, P) values and the int32 argmax (flat h * W + w, -1 for an empty bin) are
+// written with coalesced stores.  Exact: the bounds are the fp32 expressions of the reference (-ffp-contract=off), the scan is
+// raster order with a strict >, so value AND argmax equal the reference's bit for bit.
+__global__ __launch_bounds__(256) void roi_pool_fwd_kernel(const float* __restrict__ feat, const float* __restrict__ rois,
+                                                           float* __restrict__ out, int32_t* __restrict__ argmax, int N, int C, int H,
+                                                           int W, int P, float scale)
+{
+    extern __shared__ int bnd[];                     // hstart[P] | hend[P] | wstart[P] | wend[P]
+    const int r = blockIdx.x;
+    const float* roi = rois + 5 * (size_t)r;
+    const int b = (int)roi[0];
+    for (int t = threadIdx.x; t < 2 * P; t += 256) {
+        const bool isx = t >= P;
+        const int pb = isx ? t - P : t, L = isx ? W : H;
+        const int rs = (int)roundf((isx ? roi[1] : roi[2]) * scale), re = (int)roundf((isx ? roi[3] : roi[4]) * scale);
+        const int ext = max(re - rs + 1, 1);
+        const float bsz = (float)ext / (float)P;
+        const int s0 = (int)floorf((float)pb * bsz), e0 = (int)ceilf((float)(pb + 1) * bsz);
+        bnd[(isx ? 2 * P : 0) + pb] = min(max(s0 + rs, 0), L);
+        bnd[(isx ? 3 * P : P) + pb] = min(max(e0 + rs, 0), L);
+    }
+    __syncthreads();
+    const int PP = P * P, total = C * PP;
+    const bool img_ok = b >= 0 && b < N;              // (a row naming no image pools nothing)
+    const float* fb = feat + (size_t)(img_ok ? b : 0) * C * H * W;
+    float* ob = out + (size_t)r * total;
+    int32_t* ab = argmax + (size_t)r * total;
+    for (int i = threadIdx.x; i < total; i += 256) {
+        const int c = i / PP, rem = i - c * PP;
+        const int ph = rem / P, pw = rem - ph * P;
+        const int hs = bnd[ph], he = bnd[P + ph], ws = bnd[2 * P + pw], we = bnd[3 * P + pw];
+        const bool empty = he <= hs || we <= ws || !img_ok;
+        const float* f = fb + (size_t)c * H * W;
+        float m = empty ? 0.f : -FLT_MAX;
+        int am = -1;
+        if (!empty)
+            for (int y = hs; y < he; ++y)
+                for (int x = ws; x < we; ++x) {
+                    const float val = f[y * W + x];
+                    if (val > m) { m = val; am = y * W + x; }
+                }
+        ob[i] = m;
+        ab[i] = am;
+    }
+}
+
+// dfeat[b, c, argmax] += dout[r, c, ph, pw]: hardware fp32 atomics on a zeroed dfeat (neighbouring bins share their border cells
+// and ROIs overlap, so several contributions can meet in one cell: their order, hence the last bit of the sum, varies run to run)
+__global__ __launch_bounds__(256) void roi_pool_bwd_kernel(const float* __restrict__ dout, const int32_t* __restrict__ argmax,
+                                                           const float* __restrict__ rois, float* __restrict__ dfeat, int N, int C,
+                                                           int HW, int PP)
+{
+    const int r = blockIdx.x;
+    const int b = (int)rois[5 * (size_t)r];
+    if (b < 0 || b >= N) return;
+    const int total = C * PP;
+    float* fb = dfeat + (size_t)b * C * HW;
+    const float* ob = dout + (size_t)r * total;
+    const int32_t* ab = argmax + (size_t)r * total;
+    for (int i = threadIdx.x; i < total; i += 256) {
+        const int am = ab[i];
+        if (am >= 0 && am < HW) atomicAdd(fb + (size_t)(i / PP) * HW + am, ob[i]);
+    }
 }
 
 }  // namespace
 
 extern "C" {
 
+#define ROI_VARIANT_ARGS(name)                                                                                              \
+    PTMI_CHECK_ARG((aligned == 0 || aligned == 1) && sampling_ratio >= 0, name ": aligned = %d (0 or 1), sampling_ratio = %d (>= 0)", \
+                   aligned, sampling_ratio);                                                                               \
+    const RoiVariant v{aligned, sampling_ratio}
+
 int ptmi_roi_align_fwd(const float* feat, const float* rois, float* out, int n, int c, int h, int w, int r,
                        int pooled, float scale, ptmi_stream_t s)
 {
-    if (r == 0) return 0;
-    PTMI_CHECK_ARG(feat && out && rois && n > 0 && c > 0 && h > 0 && w > 0 && r > 0 && pooled > 0,
-                   "roi_align_fwd: bad args");
-    hipLaunchKernelGGL(roi_align_fwd_kernel, dim3(r), dim3(256), 0, (hipStream_t)s, feat, rois, out, c, h, w, pooled,
-                       scale);
-    PTMI_LAUNCH_CHECK("roi_align_fwd");
-    return 0;
+    return roi_fwd_launch(feat, rois, out, n, c, h, w, r, pooled, scale, (hipStream_t)s);
+}
+
+int ptmi_roi_align_fwd_ex(const float* feat, const float* rois, float* out, int n, int c, int h, int w, int r,
+                          int pooled, float scale, ptmi_stream_t s, int aligned, int sampling_ratio)
+{
+    ROI_VARIANT_ARGS("roi_align_fwd_ex");
+    return roi_fwd_launch(feat, rois, out, n, c, h, w, r, pooled, scale, (hipStream_t)s, v);
 }
 
 int ptmi_roi_align_bwd(const float* dout, const float* rois, float* dfeat, int n, int c, int h, int w, int r,
                        int pooled, float scale, ptmi_stream_t s)
 {
-    if (r == 0) return 0;
-    PTMI_CHECK_ARG(dout && dfeat && rois && n > 0 && c > 0 && h > 0 && w > 0 && r > 0 && pooled > 0,
-                   "roi_align_bwd: bad args");
-    hipLaunchKernelGGL(roi_align_bwd_kernel, dim3(r), dim3(256), 0, (hipStream_t)s, dout, rois, dfeat, c, h, w, pooled,
-                       scale);
-    PTMI_LAUNCH_CHECK("roi_align_bwd");
-    return 0;
+    return roi_bwd_launch(dout, rois, dfeat, n, c, h, w, r, pooled, scale, (hipStream_t)s);
+}
+
+int ptmi_roi_align_bwd_ex(const float* dout, const float* rois, float* dfeat, int n, int c, int h, int w, int r,
+                          int pooled, float scale, ptmi_stream_t s, int aligned, int sampling_ratio)
+{
+    ROI_VARIANT_ARGS("roi_align_bwd_ex");
+    return roi_bwd_launch(dout, rois, dfeat, n, c, h, w, r, pooled, scale, (hipStream_t)s, v);
 }
 
 int64_t ptmi_roi_align_ws_bytes(int r, int h, int w)
@@ -553,12 +805,15 @@ int64_t ptmi_roi_align_ws_bytes(int r, int h, int w)
 int ptmi_roi_align_fwd_grouped(const float* feat, const float* rois, const int32_t* img_offsets, float* out, void* ws,
                                int n, int c, int h, int w, int r, int pooled, float scale, ptmi_stream_t s)
 {
-    if (r == 0) return 0;
-    PTMI_CHECK_ARG(feat && rois && img_offsets && out && n > 0 && c > 0 && h > 0 && w > 0 && r > 0 && pooled > 0,
-                   "roi_align_fwd_grouped: bad args");
-    if (!roi_fwd_planes(c, h, w, pooled) || !ws)
-        return ptmi_roi_align_fwd(feat, rois, out, n, c, h, w, r, pooled, scale, s);
-    return roi_fwd_grouped_launch<false>(feat, rois, img_offsets, out, ws, n, c, h, w, r, scale, nullptr, nullptr, (hipStream_t)s);
+    return roi_fwd_grouped(feat, rois, img_offsets, out, ws, n, c, h, w, r, pooled, scale, (hipStream_t)s);
+}
+
+int ptmi_roi_align_fwd_grouped_ex(const float* feat, const float* rois, const int32_t* img_offsets, float* out, void* ws,
+                                  int n, int c, int h, int w, int r, int pooled, float scale, ptmi_stream_t s, int aligned,
+                                  int sampling_ratio)
+{
+    ROI_VARIANT_ARGS("roi_align_fwd_grouped_ex");
+    return roi_fwd_grouped(feat, rois, img_offsets, out, ws, n, c, h, w, r, pooled, scale, (hipStream_t)s, v);
 }
 
 int ptmi_roi_align_fwd_p8m_fits(int c, int h, int w, int pooled) { return roi_fwd_planes(c, h, w, pooled) > 0 && (c * pooled * pooled) % 8 == 0; }
@@ -588,37 +843,40 @@ int64_t ptmi_roi_align_bwd_ws_bytes(int r, int h, int w)
 int ptmi_roi_align_bwd_grouped(const float* dout, const float* rois, const int32_t* img_offsets, float* dfeat, void* ws,
                                int n, int c, int h, int w, int r, int pooled, float scale, ptmi_stream_t s)
 {
-    PTMI_CHECK_ARG(dfeat && img_offsets && n > 0 && c > 0 && h > 0 && w > 0 && r >= 0 && pooled > 0,
-                   "roi_align_bwd_grouped: bad args");
-    hipStream_t st = (hipStream_t)s;
-    const size_t plane_bytes = (size_t)h * w * sizeof(float);
-    // the band kernel: RB3_WAVES row bands (at most 32 rows each), up to four channel planes per workgroup at a pitch of
-    // 16 (mod 64) floats, two workgroups per CU if they fit, one otherwise
-    const int nb = RB3_WAVES, br = cdiv(h, nb);
-    const int pitch = ((h * w + 47) / 64) * 64 + 16;
-    const size_t strips = (size_t)nb * (64 * 4 + 4 * 52) * sizeof(float);
-    int cg = (int)((80 * 1024 - strips) / ((size_t)pitch * 4));
-    if (cg < 1) cg = (int)((160 * 1024 - strips) / ((size_t)pitch * 4));
-    if (cg > RB3_PLANES) cg = RB3_PLANES;
-    if (cg > c) cg = c;
-    const bool band_ok = pooled == 7 && ws && br <= 32 && cg >= 1;
-    if (!band_ok || r == 0) {             // not the hot-path shape (or no ROI at all): zero + atomic scatter kernel
-        hipError_t e = hipMemsetAsync(dfeat, 0, (size_t)n * c * plane_bytes, st);
-        if (e != hipSuccess) { ptmi_set_error("roi_align_bwd_grouped: memset failed"); return -2; }
-        return r == 0 ? 0 : ptmi_roi_align_bwd(dout, rois, dfeat, n, c, h, w, r, pooled, scale, s);
-    }
-    PTMI_CHECK_ARG(dout && rois, "roi_align_bwd_grouped: null buffer");
-    hipLaunchKernelGGL(roi_bwd_tables_kernel, dim3(r), dim3(64), (size_t)(h + w) * 8 * sizeof(float), st, rois, ws, h, w,
-                       scale);
-    PTMI_LAUNCH_CHECK("roi_align_bwd_tables");
-    static bool attr3 = false;
-    if (!attr3) {
-        (void)hipFuncSetAttribute((const void*)roi_align_bwd_band_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr3 = true;
-    }
-    hipLaunchKernelGGL(roi_align_bwd_band_kernel, dim3(cdiv(c, cg), n), dim3(64 * nb), (size_t)cg * pitch * 4 + strips, st, dout, ws,
-                       img_offsets, dfeat, c, h, w, cg, pitch, br);
-    PTMI_LAUNCH_CHECK("roi_align_bwd_grouped(band)");
+    return roi_bwd_grouped(dout, rois, img_offsets, dfeat, ws, n, c, h, w, r, pooled, scale, (hipStream_t)s);
+}
+
+int ptmi_roi_align_bwd_grouped_ex(const float* dout, const float* rois, const int32_t* img_offsets, float* dfeat, void* ws,
+                                  int n, int c, int h, int w, int r, int pooled, float scale, ptmi_stream_t s, int aligned,
+                                  int sampling_ratio)
+{
+    ROI_VARIANT_ARGS("roi_align_bwd_grouped_ex");
+    return roi_bwd_grouped(dout, rois, img_offsets, dfeat, ws, n, c, h, w, r, pooled, scale, (hipStream_t)s, v);
+}
+
+int ptmi_roi_pool_fwd(const float* feat, const float* rois, float* out, int32_t* argmax, int n, int c, int h, int w, int r,
+                      int pooled, float scale, ptmi_stream_t s)
+{
+    if (r == 0) return 0;
+    PTMI_CHECK_ARG(feat && rois && out && argmax && n > 0 && c > 0 && h > 0 && w > 0 && r > 0 && pooled > 0 && pooled <= 1024,
+                   "roi_pool_fwd: bad args");
+    hipLaunchKernelGGL(roi_pool_fwd_kernel, dim3(r), dim3(256), (size_t)4 * pooled * sizeof(int), (hipStream_t)s, feat, rois, out,
+                       argmax, n, c, h, w, pooled, scale);
+    PTMI_LAUNCH_CHECK("roi_pool_fwd");
+    return 0;
+}
+
+int ptmi_roi_pool_bwd(const float* dout, const int32_t* argmax, const float* rois, float* dfeat, int n, int c, int h, int w, int r,
+                      int pooled, ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(dfeat && n > 0 && c > 0 && h > 0 && w > 0 && r >= 0 && pooled > 0, "roi_pool_bwd: bad args");
+    hipError_t e = hipMemsetAsync(dfeat, 0, (size_t)n * c * h * w * sizeof(float), (hipStream_t)s);
+    if (e != hipSuccess) { ptmi_set_error("roi_pool_bwd: memset failed"); return -2; }
+    if (r == 0) return 0;
+    PTMI_CHECK_ARG(dout && argmax && rois, "roi_pool_bwd: null buffer");
+    hipLaunchKernelGGL(roi_pool_bwd_kernel, dim3(r), dim3(256), 0, (hipStream_t)s, dout, argmax, rois, dfeat, n, c, h * w,
+                       pooled * pooled);
+    PTMI_LAUNCH_CHECK("roi_pool_bwd");
     return 0;
 }
 

@@ -27,13 +27,34 @@ class _LinearP(nn.Module):
         self.bias = nn.Parameter(torch.zeros(nout))
 
 
+POOLER_TYPES = ("ROIAlignV2", "ROIAlign", "ROIPool")
+
+
 class ROIPooler(nn.Module):
-    """Single-level ROIAlignV2 pooler (D2 ROIPooler; constructed at roi_heads.py:68-73)."""
+    """Single-level pooler (D2 ROIPooler; constructed at roi_heads.py:68-73): MODEL.ROI_BOX_HEAD.POOLER_TYPE
+    "ROIAlignV2" (aligned), "ROIAlign" (detectron2's legacy, not aligned) -- both with POOLER_SAMPLING_RATIO 0 (adaptive grid) or
+    > 0 (fixed grid) -- and "ROIPool" (max pooling; the sampling ratio is ignored, as in detectron2)."""
 
     def __init__(self, output_size, scales, sampling_ratio, pooler_type):
         super().__init__()
-        assert pooler_type == "ROIAlignV2" and sampling_ratio == 0 and len(scales) == 1
+        if pooler_type not in POOLER_TYPES:
+            raise ValueError(f"MODEL.ROI_BOX_HEAD.POOLER_TYPE: {pooler_type!r} is not supported (one of {', '.join(POOLER_TYPES)})")
+        if int(sampling_ratio) != sampling_ratio or sampling_ratio < 0:
+            raise ValueError(f"MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO: expected an integer >= 0, got {sampling_ratio!r}")
+        if len(scales) != 1:
+            raise ValueError(f"MODEL.ROI_HEADS.IN_FEATURES: {len(scales)} feature levels; multi-level (FPN) ROI pooling is not "
+                             "supported, the pooler takes exactly one")
         self.output_size, self.scale = int(output_size), float(scales[0])
+        self.pooler_type, self.sampling_ratio = pooler_type, int(sampling_ratio)
+        # the operator is resolved once (as box_regression.uncertainty_losses does for the loss pair)
+        if pooler_type == "ROIPool":
+            self._pool = lambda feat, rois, img_offsets: ops.roi_pool(feat, rois, self.output_size, self.scale)
+        else:
+            aligned = pooler_type == "ROIAlignV2"
+            self._pool = lambda feat, rois, img_offsets: ops.roi_align(feat, rois, self.output_size, self.scale, img_offsets,
+                                                                       aligned, self.sampling_ratio)
+        # the fused ROIAlign -> fc1 bf16 operand writer (SOLVER.AMP.ENABLED) exists for ROIAlignV2 with the adaptive grid only
+        self.defers = pooler_type == "ROIAlignV2" and self.sampling_ratio == 0
 
     def forward(self, x: List[torch.Tensor], box_lists: List[Boxes]) -> torch.Tensor:
         dev = x[0].device
@@ -51,12 +72,13 @@ class ROIPooler(nn.Module):
             rois = torch.cat([img_col.unsqueeze(1), torch.cat([b.tensor for b in box_lists], 0)], 1)
         # (ops.dev_i32: pinned + asynchronous -- torch.tensor(list, device=...) copies from pageable memory, which waits for the stream)
         img_offsets = ops.dev_i32(offs, dev) if len(box_lists) == x[0].shape[0] else None
-        if (img_offsets is not None and offs[-1] > 0 and ops._native_bf16() and x[0].is_cuda
+        if (self.defers and img_offsets is not None and offs[-1] > 0 and ops._native_bf16() and x[0].is_cuda
                 and ops.roi_align_p8m_fits(x[0].shape[1], x[0].shape[2], x[0].shape[3], self.output_size)):
             # SOLVER.AMP.ENABLED: the pooling is deferred to its consumer -- the box head's first Linear layer takes its bf16
             # operands straight from the ROIAlign kernel (p8._RoiAlignLinearP8)
             return DeferredROIAlign(x[0], rois.contiguous(), img_offsets, self.output_size, self.scale)
-        return ops.roi_align(x[0], rois.contiguous(), self.output_size, self.scale, img_offsets)
+        # every other setting: the materialised fp32 tensor (the box head takes its ordinary ops.linear route)
+        return self._pool(x[0], rois.contiguous(), img_offsets)
 
 
 class DeferredROIAlign:

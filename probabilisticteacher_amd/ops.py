@@ -769,51 +769,63 @@ def conv1x1(x, weight, bias):
 
 
 # ============================================================================ ROIAlign
+def _roi_variant(aligned, sampling_ratio) -> Tuple[int, int]:
+    aligned, sampling_ratio = int(bool(aligned)), int(sampling_ratio)
+    if sampling_ratio < 0:
+        raise ValueError(f"roi_align: sampling_ratio must be >= 0, got {sampling_ratio}")
+    return aligned, sampling_ratio
+
+
 class _ROIAlign(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, rois, pooled: int, scale: float, img_offsets):
+    def forward(ctx, feat, rois, pooled: int, scale: float, img_offsets, aligned: int = 1, sampling_ratio: int = 0):
         feat = _chk(feat.contiguous())
         rois = _chk(rois.contiguous())
         n, c, h, w = feat.shape
         r = rois.shape[0]
         out = torch.empty((r, c, pooled, pooled), dtype=F32, device=feat.device)
+        # (aligned, sampling_ratio) = (1, 0), ROIAlignV2 with the adaptive grid, keeps its own entry points and kernels
+        sfx, var = ("", ()) if (aligned, sampling_ratio) == (1, 0) else ("_ex", (aligned, sampling_ratio))
         with _prof("roi_align_fwd"):
             if img_offsets is not None:
                 ws = torch.empty(_lib.load().ptmi_roi_align_ws_bytes(r, h, w), dtype=torch.uint8, device=feat.device)
-                _lib.call("ptmi_roi_align_fwd_grouped", _ptr(feat), _ptr(rois), _ptr(_chk(img_offsets, torch.int32)),
-                          _ptr(out), _ptr(ws), n, c, h, w, r, pooled, float(scale), _stream())
+                _lib.call("ptmi_roi_align_fwd_grouped" + sfx, _ptr(feat), _ptr(rois), _ptr(_chk(img_offsets, torch.int32)),
+                          _ptr(out), _ptr(ws), n, c, h, w, r, pooled, float(scale), _stream(), *var)
             else:
-                _lib.call("ptmi_roi_align_fwd", _ptr(feat), _ptr(rois), _ptr(out), n, c, h, w, r, pooled, float(scale),
-                          _stream())
+                _lib.call("ptmi_roi_align_fwd" + sfx, _ptr(feat), _ptr(rois), _ptr(out), n, c, h, w, r, pooled, float(scale),
+                          _stream(), *var)
         ctx.save_for_backward(rois, img_offsets)
-        ctx.meta = (n, c, h, w, pooled, float(scale))
+        ctx.meta = (n, c, h, w, pooled, float(scale), aligned, sampling_ratio)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         rois, img_offsets = ctx.saved_tensors
-        n, c, h, w, pooled, scale = ctx.meta
+        n, c, h, w, pooled, scale, aligned, sampling_ratio = ctx.meta
         dout = _chk(dout.contiguous())
         if img_offsets is not None:
             # rois grouped by image: LDS-accumulating kernel, no global atomics, writes every element of dfeat
-            dfeat = roi_align_bwd_grouped(dout, rois, img_offsets, n, c, h, w, pooled, scale)
+            dfeat = roi_align_bwd_grouped(dout, rois, img_offsets, n, c, h, w, pooled, scale, aligned, sampling_ratio)
         else:
             dfeat = torch.zeros((n, c, h, w), dtype=F32, device=dout.device)
+            sfx, var = ("", ()) if (aligned, sampling_ratio) == (1, 0) else ("_ex", (aligned, sampling_ratio))
             with _prof("roi_align_bwd"):
-                _lib.call("ptmi_roi_align_bwd", _ptr(dout), _ptr(rois), _ptr(dfeat), n, c, h, w, rois.shape[0], pooled,
-                          scale, _stream())
-        return dfeat, None, None, None, None
+                _lib.call("ptmi_roi_align_bwd" + sfx, _ptr(dout), _ptr(rois), _ptr(dfeat), n, c, h, w, rois.shape[0], pooled,
+                          scale, _stream(), *var)
+        return dfeat, None, None, None, None, None, None
 
 
 def roi_align_bwd_grouped(dout: torch.Tensor, rois: torch.Tensor, img_offsets: torch.Tensor, n: int, c: int, h: int, w: int,
-                          pooled: int, scale: float) -> torch.Tensor:
+                          pooled: int, scale: float, aligned=True, sampling_ratio: int = 0) -> torch.Tensor:
     """d(feature map) (n, c, h, w) from the gradient of ROIAlign's output (R, c * pooled * pooled) for rois grouped by image"""
+    aligned, sampling_ratio = _roi_variant(aligned, sampling_ratio)
     dout = _chk(dout.contiguous())
     dfeat = torch.empty((n, c, h, w), dtype=F32, device=dout.device)
+    sfx, var = ("", ()) if (aligned, sampling_ratio) == (1, 0) else ("_ex", (aligned, sampling_ratio))
     with _prof("roi_align_bwd"):
         ws = torch.empty(_lib.load().ptmi_roi_align_bwd_ws_bytes(rois.shape[0], h, w), dtype=torch.uint8, device=dout.device)
-        _lib.call("ptmi_roi_align_bwd_grouped", _ptr(dout), _ptr(rois), _ptr(_chk(img_offsets, torch.int32)), _ptr(dfeat), _ptr(ws),
-                  n, c, h, w, rois.shape[0], pooled, scale, _stream())
+        _lib.call("ptmi_roi_align_bwd_grouped" + sfx, _ptr(dout), _ptr(rois), _ptr(_chk(img_offsets, torch.int32)), _ptr(dfeat),
+                  _ptr(ws), n, c, h, w, rois.shape[0], pooled, scale, _stream(), *var)
     return dfeat
 
 
@@ -838,10 +850,51 @@ def roi_align_p8m(feat: torch.Tensor, rois: torch.Tensor, img_offsets: torch.Ten
     return xk, xt
 
 
-def roi_align(feat, rois, pooled: int, scale: float, img_offsets=None):
+def roi_align(feat, rois, pooled: int, scale: float, img_offsets=None, aligned=True, sampling_ratio: int = 0):
     """rois (R,5) = [image index, x1, y1, x2, y2].  If the rows are grouped by image, pass `img_offsets`
-    (int32 (N+1,) device tensor of row offsets) to enable the atomic-free backward."""
-    return _ROIAlign.apply(feat, rois, pooled, scale, img_offsets)
+    (int32 (N+1,) device tensor of row offsets) to enable the atomic-free backward.
+    `aligned` / `sampling_ratio`: torchvision roi_align's (detectron2 "ROIAlignV2" = aligned, "ROIAlign" = not aligned;
+    sampling_ratio 0 = ceil(roi extent / pooled) samples a bin side)."""
+    aligned, sampling_ratio = _roi_variant(aligned, sampling_ratio)
+    return _ROIAlign.apply(feat, rois, pooled, scale, img_offsets, aligned, sampling_ratio)
+
+
+# ============================================================================ ROIPool
+class _ROIPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, rois, pooled: int, scale: float):
+        feat = _chk(feat.contiguous())
+        rois = _chk(rois.contiguous())
+        n, c, h, w = feat.shape
+        r = rois.shape[0]
+        out = torch.empty((r, c, pooled, pooled), dtype=F32, device=feat.device)
+        argmax = torch.empty((r, c, pooled, pooled), dtype=torch.int32, device=feat.device)
+        with _prof("roi_pool_fwd"):
+            _lib.call("ptmi_roi_pool_fwd", _ptr(feat), _ptr(rois), _ptr(out), _ptr(argmax), n, c, h, w, r, pooled, float(scale),
+                      _stream())
+        ctx.save_for_backward(rois, argmax)
+        ctx.meta = (n, c, h, w, pooled)
+        ctx.mark_non_differentiable(argmax)
+        return out, argmax
+
+    @staticmethod
+    def backward(ctx, dout, _dargmax):
+        rois, argmax = ctx.saved_tensors
+        n, c, h, w, pooled = ctx.meta
+        dout = _chk(dout.contiguous())
+        dfeat = torch.empty((n, c, h, w), dtype=F32, device=dout.device)        # (zeroed by the entry point)
+        with _prof("roi_pool_bwd"):
+            _lib.call("ptmi_roi_pool_bwd", _ptr(dout), _ptr(argmax), _ptr(rois), _ptr(dfeat), n, c, h, w, rois.shape[0], pooled,
+                      _stream())
+        return dfeat, None, None, None
+
+
+def roi_pool(feat, rois, pooled: int, scale: float, return_argmax: bool = False):
+    """torchvision roi_pool: the maximum over each bin's integer cells; rois (R,5) = [image index, x1, y1, x2, y2].  The int32
+    argmax (flat h * W + w of the first maximum in raster order, -1 for an empty bin) is saved for the backward (an atomic
+    scatter: the feature-map gradient's summation order varies run to run) and returned on request."""
+    out, argmax = _ROIPool.apply(feat, rois, pooled, scale)
+    return (out, argmax) if return_argmax else out
 
 
 # ============================================================================ boxes

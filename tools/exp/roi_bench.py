@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """tools/exp/roi_bench.py -- ROIAlign forward / backward at the step's launch shapes, ROI extents drawn like the bench's
-(tools/exp/roi_stats.py: median 11 x 12.5 feature cells, 1 % wider than 55).   python tools/exp/roi_bench.py [--lib other.so]"""
+(tools/exp/roi_stats.py: median 11 x 12.5 feature cells, 1 % wider than 55).
+    python tools/exp/roi_bench.py [--lib other.so] [--variants v2,align,align_r2,v2_r2,pool]
+--variants: the pooler settings to time (MODEL.ROI_BOX_HEAD.POOLER_TYPE / POOLER_SAMPLING_RATIO); default: ROIAlignV2, ratio 0."""
 import argparse
 import os
 import sys
@@ -34,10 +36,21 @@ def rois_like_the_step(n, per, g):
     return torch.stack([img, x1, y1, x2, y2], 1)
 
 
+# name -> pooling call on (feat, rois, img_offsets)
+VARIANTS = {
+    "v2": lambda f, r, o: ops.roi_align(f, r, 7, 1 / 16, o),
+    "align": lambda f, r, o: ops.roi_align(f, r, 7, 1 / 16, o, False, 0),
+    "align_r2": lambda f, r, o: ops.roi_align(f, r, 7, 1 / 16, o, False, 2),
+    "v2_r2": lambda f, r, o: ops.roi_align(f, r, 7, 1 / 16, o, True, 2),
+    "pool": lambda f, r, o: ops.roi_pool(f, r, 7, 1 / 16),
+}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default="")
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--variants", default="v2")
     a = ap.parse_args()
     if a.lib:
         _lib.LIB_PATH = os.path.abspath(a.lib)
@@ -49,16 +62,19 @@ def main():
         wc = (rois[:, 3] - rois[:, 1]) / 16
         hc = (rois[:, 4] - rois[:, 2]) / 16
         offs = torch.arange(0, (n + 1) * per, per, dtype=torch.int32, device=dev)
-        out = ops.roi_align(feat, rois, 7, 1 / 16, offs)
-        ms = timeit(lambda: ops.roi_align(feat, rois, 7, 1 / 16, offs), a.iters)
-        print(f"n={n} R={n * per} (median {float(wc.median()):.1f} x {float(hc.median()):.1f} cells): fwd {ms:7.3f} ms "
-              f"({out.numel() * 4 / ms / 1e6:6.1f} GB/s of output)", end="")
-        if grad:
-            go = torch.randn_like(out)
-            ms = timeit(lambda: torch.autograd.grad(out, feat, go, retain_graph=True), a.iters)
-            print(f"   bwd {ms:7.3f} ms", end="")
-        print(flush=True)
-        del feat, out
+        for name in a.variants.split(","):
+            pool = VARIANTS[name]
+            out = pool(feat, rois, offs)
+            ms = timeit(lambda: pool(feat, rois, offs), a.iters)
+            print(f"{name:9s} n={n} R={n * per} (median {float(wc.median()):.1f} x {float(hc.median()):.1f} cells): fwd {ms:7.3f} ms "
+                  f"({out.numel() * 4 / ms / 1e6:6.1f} GB/s of output)", end="")
+            if grad:
+                go = torch.randn_like(out)
+                ms = timeit(lambda: torch.autograd.grad(out, feat, go, retain_graph=True), a.iters)
+                print(f"   bwd {ms:7.3f} ms", end="")
+            print(flush=True)
+            del out
+        del feat
 
 
 if __name__ == "__main__":
