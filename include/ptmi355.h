@@ -571,6 +571,13 @@ int ptmi_aug_resize_pass_batched(const int64_t* desc, int n, int64_t max_out_ele
  * Four output bytes per thread, moved as one dword where the addresses are 4-byte aligned and as bytes where not. */
 int ptmi_aug_resize_window_pass_batched(const int64_t* wdesc, int n, int64_t max_out_elems, ptmi_stream_t s);
 int ptmi_aug_flip_window_batched(const int64_t* wdesc, int n, int64_t max_elems, ptmi_stream_t s);
+/* Decoded image -> record format: the HWC -> CHW transpose and the BGR swap of read_image (D2 detection_utils.read_image +
+ * dataset_mapper.py:162-169) for the loader's decode workers, which stage Pillow's packed RGB bytes as they are.
+ * `desc` is a DEVICE table of 8 int64 words per image: [src packed u8 (h,w,3), dst planar u8 (3,h,w), h, w, p4, 0, 0, 0];
+ * p4 = 0 keeps the channel order, 1 reverses it (RGB -> BGR).  src may start at any byte address; src != dst.
+ * max_pixels = max_i h_i*w_i (sizes the grid).  Four pixels per thread: three dword loads and one dword store per plane
+ * where the addresses are 4-byte aligned, bytes where not. */
+int ptmi_aug_unpack_hwc_batched(const int64_t* desc, int n, int64_t max_pixels, ptmi_stream_t s);
 
 /* ------------------------------------------------------------------ diagnostics
  * CU-contention probe (round 6; no counterpart in the reference): n_cus workgroups that each hold one CU (64 KB of LDS: no

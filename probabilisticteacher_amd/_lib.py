@@ -138,6 +138,7 @@ SIGNATURES = {
     "ptmi_aug_resize_pass_batched": (_i, [_vp, _i, _i64, _vp]),
     "ptmi_aug_resize_window_pass_batched": (_i, [_vp, _i, _i64, _vp]),
     "ptmi_aug_flip_window_batched": (_i, [_vp, _i, _i64, _vp]),
+    "ptmi_aug_unpack_hwc_batched": (_i, [_vp, _i, _i64, _vp]),
 }
 
 _lib = None

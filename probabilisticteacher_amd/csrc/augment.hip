@@ -367,6 +367,47 @@ __global__ __launch_bounds__(256) void aug_resize_window_pass_kernel(const int64
     }
 }
 
+// ---------------------------------------------------------------- decoded image -> record format
+// Pillow hands a decoded image over as packed (H, W, 3) RGB bytes; the records are planar (3, H, W), BGR by default
+// (data/datasets.py read_image: arr[:, :, ::-1].transpose(2, 0, 1)).  desc: 8 int64 words per image,
+//   [0] src packed (h, w, 3), [1] dst planar (3, h, w), [2] h, [3] w, [4] 0 keeps the channel order / 1 reverses it.
+// A thread owns four consecutive pixels of one row: 12 source bytes, as three dwords where the address is 4-byte aligned
+// (a wave then reads 768 contiguous bytes) and byte by byte where not or in a row's short last quad, and one quad per plane
+// (store_quad: a dword where aligned).  6 bytes of traffic per pixel, no reuse, no LDS.
+__global__ __launch_bounds__(256) void aug_unpack_hwc_kernel(const int64_t* __restrict__ desc)
+{
+    const int64_t* d = desc + 8 * (int64_t)blockIdx.y;
+    const uint8_t* src = (const uint8_t*)d[0];
+    uint8_t* dst = (uint8_t*)d[1];
+    const int h = (int)d[2], w = (int)d[3], reverse = (int)d[4];
+    const int qpr = (w + 3) >> 2;                       // quads per row
+    const int64_t total = (int64_t)h * qpr, plane = (int64_t)h * w;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
+        const int ox = (int)(q % qpr) * 4;
+        const int64_t y = q / qpr;
+        const int n = w - ox < 4 ? w - ox : 4;
+        const int64_t pix = y * w + ox;
+        const uint8_t* p = src + 3 * pix;
+        uint32_t a0 = 0, a1 = 0, a2 = 0;                // source bytes 0..3, 4..7, 8..11
+        if (n == 4 && ((uintptr_t)p & 3) == 0) {
+            const uint32_t* p4 = reinterpret_cast<const uint32_t*>(p);
+            a0 = p4[0]; a1 = p4[1]; a2 = p4[2];
+        } else {
+            for (int j = 0; j < 3 * n; ++j) {
+                const uint32_t b = (uint32_t)p[j] << (8 * (j & 3));
+                if (j < 4) a0 |= b; else if (j < 8) a1 |= b; else a2 |= b;
+            }
+        }
+        const uint32_t c0 = (a0 & 255u) | ((a0 >> 24) << 8) | (((a1 >> 16) & 255u) << 16) | (((a2 >> 8) & 255u) << 24);
+        const uint32_t c1 = ((a0 >> 8) & 255u) | ((a1 & 255u) << 8) | ((a1 >> 24) << 16) | (((a2 >> 16) & 255u) << 24);
+        const uint32_t c2 = ((a0 >> 16) & 255u) | (((a1 >> 8) & 255u) << 8) | ((a2 & 255u) << 16) | ((a2 >> 24) << 24);
+        uint8_t* o = dst + pix;
+        store_quad(o, reverse ? c2 : c0, n);
+        store_quad(o + plane, c1, n);
+        store_quad(o + 2 * plane, reverse ? c0 : c2, n);
+    }
+}
+
 inline dim3 grid_for(int n, int64_t max_elems)
 {
     int64_t bx = (max_elems + 1023) / 1024;
@@ -444,6 +485,15 @@ int ptmi_aug_flip_window_batched(const int64_t* wdesc, int n, int64_t max_elems,
     PTMI_CHECK_ARG(wdesc && n > 0 && n < 65536 && max_elems > 0, "aug_flip_window_batched: bad args");
     hipLaunchKernelGGL(aug_flip_window_kernel, grid_for(n, max_elems), dim3(256), 0, (hipStream_t)s, wdesc);
     PTMI_LAUNCH_CHECK("aug_flip_window_batched");
+    return 0;
+}
+
+int ptmi_aug_unpack_hwc_batched(const int64_t* desc, int n, int64_t max_pixels, ptmi_stream_t s)
+{
+    if (n == 0) return 0;
+    PTMI_CHECK_ARG(desc && n > 0 && n < 65536 && max_pixels > 0, "aug_unpack_hwc_batched: bad args");
+    hipLaunchKernelGGL(aug_unpack_hwc_kernel, grid_for(n, max_pixels), dim3(256), 0, (hipStream_t)s, desc);
+    PTMI_LAUNCH_CHECK("aug_unpack_hwc_batched");
     return 0;
 }
 

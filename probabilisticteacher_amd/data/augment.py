@@ -143,6 +143,23 @@ def hflip_batch(images: Sequence[torch.Tensor], flips: Sequence[bool]) -> List[t
     return out
 
 
+def unpack_hwc_batch(srcs: Sequence[torch.Tensor], bgr: bool) -> List[torch.Tensor]:
+    """Decoded images as Pillow delivers them -- packed uint8 (H, W, 3) RGB device tensors, starting at any byte address -- to
+    the planar (3, H, W) record format: `arr[:, :, ::-1].transpose(2, 0, 1)` of `datasets.read_image` (bgr) or the
+    channel-preserving `arr.transpose(2, 0, 1)`.  One launch for the batch, whatever the image sizes."""
+    if not srcs:
+        return []
+    dev = srcs[0].device
+    for im in srcs:
+        _chk(im, torch.uint8, "image")
+        if im.dim() != 3 or im.shape[2] != 3 or im.numel() == 0:
+            raise ValueError(f"unpack_hwc_batch: expected a non-empty (H, W, 3) image, got {tuple(im.shape)}")
+    out = [torch.empty((3, im.shape[0], im.shape[1]), dtype=torch.uint8, device=dev) for im in srcs]
+    rows = [[im.data_ptr(), o.data_ptr(), im.shape[0], im.shape[1], int(bool(bgr)), 0, 0, 0] for im, o in zip(srcs, out)]
+    _launch("ptmi_aug_unpack_hwc_batched", rows, dev, max(im.shape[0] * im.shape[1] for im in srcs))
+    return out
+
+
 def resize_shortest_edge_size(h: int, w: int, short_edge: int, max_size: int) -> Tuple[int, int]:
     """D2 ResizeShortestEdge.get_transform: scale the short side to `short_edge`, cap the long side at `max_size`, round
     half up.  Returns (new_h, new_w)."""

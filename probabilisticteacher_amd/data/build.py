@@ -2,7 +2,12 @@
 
 Same structure as the reference -- an infinite, seeded, rank-sharded index stream per dataset (D2 TrainingSampler), the
 two-crop mapper, aspect-ratio grouping of the labelled and the unlabelled stream in lock step, per-rank batch = total / world
-(build.py:174-187) -- but the mapper is the device pipeline of data/mapper.py: the host only decodes the images."""
+(build.py:174-187) -- but the mapper is the device pipeline of data/mapper.py: the host only decodes the images.
+
+cfg.DATALOADER.NUM_WORKERS (the reference's DataLoader worker processes, build.py:205-216) is the number of decode THREADS of
+data/prefetch.py: 0 decodes and maps image by image on the consuming thread; n > 0 decodes ahead and maps a chunk of images
+per call.  The record stream is the same for every value."""
+import collections
 import itertools
 from typing import Iterable, Iterator, List, Optional
 
@@ -10,7 +15,7 @@ import torch
 import torch.distributed as dist
 
 from ..structures import Boxes, FreeInstances
-from . import datasets
+from . import datasets, prefetch
 from .augment import resize_batch, resize_shortest_edge_size
 from .mapper import AspectRatioGroupedSemiSupDatasetTwoCrop, DeviceTwoCropMapper
 
@@ -37,8 +42,52 @@ def _mapped_pairs(dicts: List[dict], sampler: Iterable[int], mapper: DeviceTwoCr
     for i in sampler:
         d = datasets.to_mapper_input(dicts[i], fmt)
         if not labelled:                     # the unlabelled stream's annotations are never used (trainer.py:248-257)
-            d = {k: v for k, v in d.items() if k not in ("boxes", "classes", "difficult")}
+            d = _drop_annotations(d)
         yield mapper([d])[0]
+
+
+def _drop_annotations(d: dict) -> dict:
+    return {k: v for k, v in d.items() if k not in ("boxes", "classes", "difficult")}
+
+
+def _prefetched_pairs(label_dicts, unlabel_dicts, samp_l, samp_u, mapper, fmt: str, chunk: int, ahead_of):
+    """The two `_mapped_pairs` streams with the decode on worker threads.  Returns (labelled stream, unlabelled stream,
+    DecodeAhead).  The decodes are submitted in the order the lock-step zip consumes the streams (l0, u0, l1, u1, ...);
+    `chunk` pairs at a time are unpacked with one launch and mapped with one mapper call per stream.  The mapper's one rng is
+    drawn per image in that same interleaved order -- `mapper.draw` on this thread -- and the draws go to the batched call
+    explicitly, so the records are those of the serial path."""
+    def items():
+        for il, iu in zip(samp_l, samp_u):
+            yield label_dicts[il]
+            yield unlabel_dicts[iu]
+    ahead = ahead_of(items())
+    queues = (collections.deque(), collections.deque())        # mapped pairs of the labelled / the unlabelled stream
+
+    def fill():
+        got = ahead.take_planar(2 * chunk, fmt == "BGR", multiple=2)
+        inputs, draws = ([], []), ([], [])
+        for k, (d, img) in enumerate(got):                     # k even: labelled, odd: unlabelled
+            m = datasets.to_mapper_input(d, fmt, image=img)
+            inputs[k % 2].append(m if k % 2 == 0 else _drop_annotations(m))
+            draws[k % 2].append(mapper.draw([tuple(img.shape[-2:])]))
+        for q, dd, dr in zip(queues, inputs, draws):
+            crops, sizes, flips, params = ([x[j][0] for x in dr] for j in range(4))
+            q.extend(mapper(dd, params=params, flips=flips, sizes=sizes, crops=crops))
+
+    def stream(q):
+        while True:
+            if not q:
+                fill()
+            yield q.popleft()
+    return stream(queues[0]), stream(queues[1]), ahead
+
+
+def _closing(it, ahead):
+    """`it`, and the decode threads stopped when the iterator is closed, dropped or fails"""
+    try:
+        yield from it
+    finally:
+        ahead.close()
 
 
 def build_detection_semisup_train_loader_two_crops(cfg, mapper: Optional[DeviceTwoCropMapper] = None, seed: int = 0):
@@ -47,36 +96,62 @@ def build_detection_semisup_train_loader_two_crops(cfg, mapper: Optional[DeviceT
     bl, bu = cfg.SOLVER.IMG_PER_BATCH_LABEL, cfg.SOLVER.IMG_PER_BATCH_UNLABEL
     assert bl > 0 and bl % world == 0, f"Total label batch size ({bl}) must be divisible by the number of gpus ({world})."
     assert bu > 0 and bu % world == 0, f"Total unlabel batch size ({bu}) must be divisible by the number of gpus ({world})."
+    workers = prefetch.num_workers(cfg)
     label_dicts = datasets.get_dataset_dicts(cfg.DATASETS.TRAIN_LABEL, filter_empty=cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS)   # build.py:111
     unlabel_dicts = datasets.get_dataset_dicts(cfg.DATASETS.TRAIN_UNLABEL, filter_empty=False)
     mapper = mapper or DeviceTwoCropMapper.from_config(cfg, seed=seed + 17 * rank)
     fmt = cfg.INPUT.FORMAT
-    lab = _mapped_pairs(label_dicts, training_sampler(len(label_dicts), seed), mapper, fmt, True)
-    unl = _mapped_pairs(unlabel_dicts, training_sampler(len(unlabel_dicts), seed + 1), mapper, fmt, False)
-    return iter(AspectRatioGroupedSemiSupDatasetTwoCrop((lab, unl), (bl // world, bu // world)))
+    samp_l, samp_u = training_sampler(len(label_dicts), seed), training_sampler(len(unlabel_dicts), seed + 1)
+    bl, bu = bl // world, bu // world
+    if workers == 0:
+        lab = _mapped_pairs(label_dicts, samp_l, mapper, fmt, True)
+        unl = _mapped_pairs(unlabel_dicts, samp_u, mapper, fmt, False)
+        return iter(AspectRatioGroupedSemiSupDatasetTwoCrop((lab, unl), (bl, bu)))
+    lab, unl, ahead = _prefetched_pairs(
+        label_dicts, unlabel_dicts, samp_l, samp_u, mapper, fmt, min(bl, bu),
+        lambda items: prefetch.DecodeAhead(items, lambda d: d["file_name"], workers, prefetch.max_in_flight(bl + bu), cfg.MODEL.DEVICE))
+    return _closing(AspectRatioGroupedSemiSupDatasetTwoCrop((lab, unl), (bl, bu)), ahead)
+
+
+def _test_record(cfg, d: dict, m: dict, dev) -> dict:
+    img = m["image"].to(dev)
+    h, w = img.shape[-2:]
+    nh, nw = resize_shortest_edge_size(h, w, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
+    rec = {"image": resize_batch([img], [(nh, nw)])[0], "height": h, "width": w, "image_id": d["image_id"],
+           "file_name": d["file_name"]}
+    if "boxes" in m:
+        inst = FreeInstances((h, w))
+        inst.gt_boxes, inst.gt_classes, inst.difficult = Boxes(m["boxes"]), m["classes"], m["difficult"]
+        rec["instances"] = inst
+    return rec
 
 
 def build_detection_test_loader(cfg, dataset_name: str, batch_size: int = 1):
     """D2 build_detection_test_loader + DatasetMapper(is_train=False): ResizeShortestEdge(MIN_SIZE_TEST, MAX_SIZE_TEST), no flip;
     records keep the ORIGINAL height / width (detector_postprocess scales the detections back) and carry the ground truth in
     original coordinates for the evaluator.  Rank r evaluates images r, r + world, ... (D2 InferenceSampler shards contiguously;
-    the evaluator gathers the shards, so the split does not matter)."""
+    the evaluator gathers the shards, so the split does not matter).  With DATALOADER.NUM_WORKERS > 0 the images are decoded
+    ahead by that many threads (look-ahead: LOOKAHEAD_STEPS x max(batch_size, workers) images); the records are the same."""
     rank, world = _rank_world()
+    workers = prefetch.num_workers(cfg)
     dicts = datasets.get_dataset_dicts([dataset_name])
     dev = torch.device(cfg.MODEL.DEVICE)
     mine = dicts[rank::world]
-    for s in range(0, len(mine), batch_size):
-        batch = []
-        for d in mine[s:s + batch_size]:
-            m = datasets.to_mapper_input(d, cfg.INPUT.FORMAT)
-            img = m["image"].to(dev)
-            h, w = img.shape[-2:]
-            nh, nw = resize_shortest_edge_size(h, w, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
-            rec = {"image": resize_batch([img], [(nh, nw)])[0], "height": h, "width": w, "image_id": d["image_id"],
-                   "file_name": d["file_name"]}
-            if "boxes" in m:
-                inst = FreeInstances((h, w))
-                inst.gt_boxes, inst.gt_classes, inst.difficult = Boxes(m["boxes"]), m["classes"], m["difficult"]
-                rec["instances"] = inst
-            batch.append(rec)
-        yield batch
+    fmt = cfg.INPUT.FORMAT
+
+    def serial():
+        for s in range(0, len(mine), batch_size):
+            yield [_test_record(cfg, d, datasets.to_mapper_input(d, fmt), dev) for d in mine[s:s + batch_size]]
+
+    def ahead_of_time():
+        ahead = prefetch.DecodeAhead(mine, lambda d: d["file_name"], workers,
+                                     prefetch.max_in_flight(max(batch_size, workers)), dev)
+        try:
+            while True:
+                got = ahead.take_planar(batch_size, fmt == "BGR")
+                if not got:
+                    return
+                yield [_test_record(cfg, d, datasets.to_mapper_input(d, fmt, image=img), dev) for d, img in got]
+        finally:
+            ahead.close()
+    return serial() if workers == 0 else ahead_of_time()

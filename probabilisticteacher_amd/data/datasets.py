@@ -6,7 +6,7 @@ Host side of the boundary: XML parsing and image decoding (Pillow) happen here; 
 the device pipeline of data/mapper.py."""
 import os
 import xml.etree.ElementTree as ET
-from typing import Callable, Dict, List, Sequence
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -86,6 +86,15 @@ def metadata(name: str) -> dict:
     return _METADATA[name]
 
 
+def read_image_hwc(file_name: str) -> np.ndarray:
+    """the decode of detection_utils.read_image alone: uint8 (H, W, 3) RGB, upright, as Pillow delivers it.  This is what
+    the loader's decode workers run (data/prefetch.py looks it up per call)."""
+    from PIL import Image, ImageOps
+    with Image.open(file_name) as im:
+        im = ImageOps.exif_transpose(im)          # D2 _apply_exif_orientation: rotated JPEGs are turned upright
+        return np.asarray(im.convert("RGB"))
+
+
 def read_image(file_name: str, fmt: str = "BGR") -> torch.Tensor:
     """detection_utils.read_image + the mapper's HWC -> CHW transpose (dataset_mapper.py:162-169): uint8 (3, H, W)"""
     from PIL import Image, ImageOps
@@ -97,9 +106,11 @@ def read_image(file_name: str, fmt: str = "BGR") -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(arr.transpose(2, 0, 1)))
 
 
-def to_mapper_input(d: dict, fmt: str = "BGR") -> dict:
-    """dataset dict -> what DeviceTwoCropMapper takes: decoded image + boxes / classes (+ difficult flags)"""
-    out = {"image": read_image(d["file_name"], fmt), "image_id": d["image_id"], "file_name": d["file_name"]}
+def to_mapper_input(d: dict, fmt: str = "BGR", image: Optional[torch.Tensor] = None) -> dict:
+    """dataset dict -> what DeviceTwoCropMapper takes: decoded image + boxes / classes (+ difficult flags).  `image`: the
+    already decoded uint8 (3, H, W) image in `fmt` order (the decode-ahead path); None: read it here."""
+    out = {"image": read_image(d["file_name"], fmt) if image is None else image, "image_id": d["image_id"],
+           "file_name": d["file_name"]}
     ann = d.get("annotations")
     if ann is not None:
         out["boxes"] = torch.tensor([a["bbox"] for a in ann], dtype=torch.float32).reshape(-1, 4)
