@@ -334,6 +334,18 @@ int ptmi_roi_pool_fwd(const float* feat, const float* rois, float* out, int32_t*
 int ptmi_roi_pool_bwd(const float* dout, const int32_t* argmax, const float* rois, float* dfeat, int n, int c, int h, int w,
                       int r, int pooled, ptmi_stream_t s);
 
+/* Order-independent pooler backwards (ops.deterministic): no floating-point atomics, every element of dfeat is a sum whose order
+ * depends on the inputs alone (image, ROI index, bin, sample), never on workgroup scheduling; dfeat is written in full.  Rows of
+ * rois / dout / argmax are grouped by image, img_offsets (n + 1, int32) as for ptmi_roi_align_bwd_grouped.
+ * ptmi_roi_align_bwd_det: every (aligned, sampling_ratio); ws of ptmi_roi_align_bwd_ws_bytes is required.  It runs the band
+ * kernel of ptmi_roi_align_bwd_grouped(_ex) -- fixed row ownership, ROIs in index order -- and FAILS where that entry would fall
+ * back to the atomic scatter (pooled != 7, h > 256, a padded plane beyond 160 KB of LDS).
+ * ptmi_roi_pool_bwd_det: a wave owns an (image, channel) plane and walks the image's ROIs in index order, bins in bin order. */
+int ptmi_roi_align_bwd_det(const float* dout, const float* rois, const int32_t* img_offsets, float* dfeat, void* ws, int n, int c,
+                           int h, int w, int r, int pooled, float scale, ptmi_stream_t s, int aligned, int sampling_ratio);
+int ptmi_roi_pool_bwd_det(const float* dout, const int32_t* argmax, const int32_t* img_offsets, float* dfeat, int n, int c, int h,
+                          int w, int r, int pooled, ptmi_stream_t s);
+
 /* ------------------------------------------------------------------ boxes (N4, N5, N9)
  * anchors: D2 DefaultAnchorGenerator / pt/modeling/anchor_generator.py:108-122: out (h*w*A,4),
  * anchor n=(y*w+x)*A+a = [x*stride,y*stride,x*stride,y*stride] + cell[a] (offset 0 folded in). */
@@ -502,6 +514,14 @@ int ptmi_laplace_kl_efl_loss(const float* q, const float* mu_p, const float* slo
 int ptmi_get_deltas_bwd_src(const float* src, const float* tgt, const float* ddeltas,
                             const int64_t* src_index, int64_t rows, float wx, float wy, float ww,
                             float wh, float* dsrc, ptmi_stream_t s);
+/* the same gradient by a fixed-order two-stage segmented reduction (no atomics; rows ascending within chunks of 4096, chunks
+ * ascending): dsrc (n_dst, 4) is WRITTEN, no zero fill needed; src_index values outside [0, n_dst) are ignored.  src_index =
+ * NULL means the identity (n_dst == rows, plain stores, no workspace).  ws: ptmi_get_deltas_bwd_src_det_ws_floats floats.  Made
+ * for many rows on few destinations: the work grows with ceil(n_dst / 64) x rows. */
+int64_t ptmi_get_deltas_bwd_src_det_ws_floats(int64_t rows, int64_t n_dst);
+int ptmi_get_deltas_bwd_src_det(const float* src, const float* tgt, const float* ddeltas,
+                                const int64_t* src_index, int64_t rows, float wx, float wy, float ww,
+                                float wh, float* dsrc, int64_t n_dst, float* ws, ptmi_stream_t s);
 
 /* ------------------------------------------------------------------ optimiser / EMA (N15-N17)
  * flat fp32 buffers.  EMA: trainer.py:431-449  t = s*(1-k) + t*k  (that evaluation order). */

@@ -95,6 +95,8 @@ SIGNATURES = {
     "ptmi_roi_align_bwd_grouped_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _i]),
     "ptmi_roi_pool_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "ptmi_roi_pool_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ptmi_roi_align_bwd_det": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _i]),
+    "ptmi_roi_pool_bwd_det": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ptmi_grid_anchors": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp]),
     "ptmi_apply_deltas": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i64, _f, _f, _f, _f, _f, _vp]),
     "ptmi_get_deltas": (_i, [_vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp]),
@@ -122,6 +124,8 @@ SIGNATURES = {
     "ptmi_laplace_nll_sum": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _vp, _vp, _vp]),
     "ptmi_laplace_kl_efl_loss": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "ptmi_get_deltas_bwd_src": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp, _vp]),
+    "ptmi_get_deltas_bwd_src_det_ws_floats": (_i64, [_i64, _i64]),
+    "ptmi_get_deltas_bwd_src_det": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp, _i64, _vp, _vp]),
     "ptmi_hold_cus": (_i, [_vp, _i, _i, _vp]),
     "ptmi_ema_update": (_i, [_vp, _vp, _i64, _f, _f, _vp]),
     "ptmi_sumsq": (_i, [_vp, _i64, _vp, _vp, _vp]),

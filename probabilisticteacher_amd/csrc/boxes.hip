@@ -113,6 +113,86 @@ __global__ void get_deltas_bwd_src_kernel(const float* __restrict__ src, const f
     }
 }
 
+// The same gradient with a fixed summation order (ptmi_get_deltas_bwd_src_det): a two-stage segmented reduction, no atomics.
+// Stage 1: workgroup (chunk, tile) takes GDS_CHUNK consecutive rows and the 64 destinations [64 tile, 64 tile + 64); 256 rows at
+// a time their gradients and destinations go to LDS, then thread (destination j = tid / 4, component k = tid % 4) adds the rows
+// that name j, in row order, and the partial goes to ws[tile][chunk][256].  Stage 2: one thread per element of dsrc adds its
+// partials in chunk order and WRITES the element (dsrc needs no zero fill).  The order -- rows ascending inside a chunk, chunks
+// ascending -- depends on (rows, n_dst) alone.  Made for many rows on few destinations (thousands of rows on 9 anchors: one
+// tile); the work grows with tiles x rows.
+constexpr int GDS_CHUNK = 4096;
+
+__device__ __forceinline__ float4 get_deltas_src_grad(const float4 s, const float4 t, const float4 g, float wx, float wy, float ww,
+                                                      float wh)
+{
+    const float sw = s.z - s.x, sh = s.w - s.y;
+    const float sx = s.x + 0.5f * sw, sy = s.y + 0.5f * sh;
+    const float tw = t.z - t.x, th = t.w - t.y;
+    const float tx = t.x + 0.5f * tw, ty = t.y + 0.5f * th;
+    const float ddx_dsx = -wx / sw, ddx_dsw = -wx * (tx - sx) / (sw * sw);
+    const float ddw_dsw = ww * (-tw / (sw * sw)) / (tw / sw + 1e-9f);
+    const float ddy_dsy = -wy / sh, ddy_dsh = -wy * (ty - sy) / (sh * sh);
+    const float ddh_dsh = wh * (-th / (sh * sh)) / (th / sh + 1e-9f);
+    const float g_sx = g.x * ddx_dsx, g_sw = g.x * ddx_dsw + g.z * ddw_dsw;
+    const float g_sy = g.y * ddy_dsy, g_sh = g.y * ddy_dsh + g.w * ddh_dsh;
+    return make_float4(0.5f * g_sx - g_sw, 0.5f * g_sy - g_sh, 0.5f * g_sx + g_sw, 0.5f * g_sy + g_sh);
+}
+
+__global__ __launch_bounds__(256) void get_deltas_bwd_src_seg_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
+                                                                     const float* __restrict__ dd, const int64_t* __restrict__ sidx,
+                                                                     int64_t rows, float wx, float wy, float ww, float wh,
+                                                                     float* __restrict__ ws)
+{
+    __shared__ __attribute__((aligned(16))) float gs[256 * 4];
+    __shared__ int ds[256];
+    const int tid = threadIdx.x, j = tid >> 2, k = tid & 3;
+    const int64_t row0 = (int64_t)blockIdx.x * GDS_CHUNK, d0 = (int64_t)blockIdx.y * 64;
+    float acc = 0.f;
+    for (int sub = 0; sub < GDS_CHUNK / 256; ++sub) {
+        const int64_t i = row0 + sub * 256 + tid;
+        int d = -1;
+        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < rows) {
+            const int64_t rel = (sidx ? sidx[i] : i) - d0;
+            if (rel >= 0 && rel < 64) {
+                d = (int)rel;
+                g = get_deltas_src_grad(reinterpret_cast<const float4*>(src)[i], reinterpret_cast<const float4*>(tgt)[i],
+                                        reinterpret_cast<const float4*>(dd)[i], wx, wy, ww, wh);
+            }
+        }
+        __syncthreads();                                         // the previous sub-chunk has been read
+        reinterpret_cast<float4*>(gs)[tid] = g;
+        ds[tid] = d;
+        __syncthreads();
+        for (int q = 0; q < 256; ++q)
+            if (ds[q] == j) acc += gs[4 * q + k];
+    }
+    ws[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid] = acc;
+}
+
+__global__ __launch_bounds__(256) void get_deltas_bwd_src_fin_kernel(const float* __restrict__ ws, int nchunks, int64_t n_dst,
+                                                                     float* __restrict__ dsrc)
+{
+    const int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x;  // element of dsrc (n_dst, 4)
+    if (e >= n_dst * 4) return;
+    const int64_t tile = e / 256;
+    const float* p = ws + (size_t)tile * nchunks * 256 + (e - tile * 256);
+    float acc = 0.f;
+    for (int c = 0; c < nchunks; ++c) acc += p[(size_t)c * 256];
+    dsrc[e] = acc;
+}
+
+// src_index = identity (row i is destination i): every element has one term, a plain store
+__global__ void get_deltas_bwd_src_rows_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
+                                               const float* __restrict__ dd, int64_t rows, float wx, float wy, float ww, float wh,
+                                               float* __restrict__ dsrc)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x)
+        reinterpret_cast<float4*>(dsrc)[i] = get_deltas_src_grad(reinterpret_cast<const float4*>(src)[i],
+                                                                 reinterpret_cast<const float4*>(tgt)[i],
+                                                                 reinterpret_cast<const float4*>(dd)[i], wx, wy, ww, wh);
+}
+
 // ---------------------------------------------------------------------------------- IoU + Matcher
 __device__ __forceinline__ float iou_pair(const float4 g, float garea, const float4 b, float barea)
 {
@@ -618,6 +698,38 @@ int ptmi_get_deltas_bwd_src(const float* src, const float* tgt, const float* dde
     hipLaunchKernelGGL(get_deltas_bwd_src_kernel, dim3(grid_for(rows)), dim3(256), 0, (hipStream_t)s, src, tgt,
                        ddeltas, src_index, rows, wx, wy, ww, wh, dsrc);
     PTMI_LAUNCH_CHECK("get_deltas_bwd_src");
+    return 0;
+}
+
+int64_t ptmi_get_deltas_bwd_src_det_ws_floats(int64_t rows, int64_t n_dst)
+{
+    const int64_t chunks = rows > 0 ? cdiv64(rows, GDS_CHUNK) : 1, tiles = n_dst > 0 ? cdiv64(n_dst, 64) : 1;
+    return chunks * tiles * 256;
+}
+
+int ptmi_get_deltas_bwd_src_det(const float* src, const float* tgt, const float* ddeltas, const int64_t* src_index,
+                                int64_t rows, float wx, float wy, float ww, float wh, float* dsrc, int64_t n_dst, float* ws,
+                                ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(dsrc && rows >= 0 && n_dst >= 0 && (rows == 0 || (src && tgt && ddeltas)), "get_deltas_bwd_src_det: bad args");
+    if (n_dst == 0) return 0;
+    if (!src_index) {                    // identity: destination i = row i
+        PTMI_CHECK_ARG(n_dst == rows, "get_deltas_bwd_src_det: no src_index means n_dst (%lld) == rows (%lld)", (long long)n_dst,
+                       (long long)rows);
+        hipLaunchKernelGGL(get_deltas_bwd_src_rows_kernel, dim3(grid_for(rows)), dim3(256), 0, (hipStream_t)s, src, tgt, ddeltas,
+                           rows, wx, wy, ww, wh, dsrc);
+        PTMI_LAUNCH_CHECK("get_deltas_bwd_src_det(rows)");
+        return 0;
+    }
+    const int64_t chunks = rows > 0 ? cdiv64(rows, GDS_CHUNK) : 1, tiles = cdiv64(n_dst, 64);
+    PTMI_CHECK_ARG(ws && tiles <= 65535 && chunks <= (1 << 30), "get_deltas_bwd_src_det: no workspace, or n_dst = %lld > 64 * 65535",
+                   (long long)n_dst);
+    hipLaunchKernelGGL(get_deltas_bwd_src_seg_kernel, dim3((unsigned)chunks, (unsigned)tiles), dim3(256), 0, (hipStream_t)s, src, tgt,
+                       ddeltas, src_index, rows, wx, wy, ww, wh, ws);
+    PTMI_LAUNCH_CHECK("get_deltas_bwd_src_det(seg)");
+    hipLaunchKernelGGL(get_deltas_bwd_src_fin_kernel, dim3((unsigned)cdiv64(n_dst * 4, 256)), dim3(256), 0, (hipStream_t)s, ws,
+                       (int)chunks, n_dst, dsrc);
+    PTMI_LAUNCH_CHECK("get_deltas_bwd_src_det(fin)");
     return 0;
 }
 

@@ -655,8 +655,8 @@ static int roi_fwd_grouped(const float* feat, const float* rois, const int32_t* 
 }
 
 template <class... V>
-static int roi_bwd_grouped(const float* dout, const float* rois, const int32_t* img_offsets, float* dfeat, void* ws, int n, int c,
-                           int h, int w, int r, int pooled, float scale, hipStream_t st, V... v)
+static int roi_bwd_grouped(bool band_only, const float* dout, const float* rois, const int32_t* img_offsets, float* dfeat, void* ws,
+                           int n, int c, int h, int w, int r, int pooled, float scale, hipStream_t st, V... v)
 {
     PTMI_CHECK_ARG(dfeat && img_offsets && n > 0 && c > 0 && h > 0 && w > 0 && r >= 0 && pooled > 0,
                    "roi_align_bwd_grouped: bad args");
@@ -671,6 +671,11 @@ static int roi_bwd_grouped(const float* dout, const float* rois, const int32_t* 
     if (cg > RB3_PLANES) cg = RB3_PLANES;
     if (cg > c) cg = c;
     const bool band_ok = pooled == 7 && ws && br <= 32 && cg >= 1;
+    if (band_only && !band_ok) {          // the deterministic entry: the atomic scatter kernel is not an option
+        ptmi_set_error("roi_align_bwd_det: shape (h=%d w=%d pooled=%d) is not served by the atomic-free band kernel "
+                       "(pooled = 7, h <= %d, one padded plane within 160 KB of LDS)", h, w, pooled, 32 * RB3_WAVES);
+        return -1;
+    }
     if (!band_ok || r == 0) {             // not the hot-path shape (or no ROI at all): zero + atomic scatter kernel
         hipError_t e = hipMemsetAsync(dfeat, 0, (size_t)n * c * plane_bytes, st);
         if (e != hipSuccess) { ptmi_set_error("roi_align_bwd_grouped: memset failed"); return -2; }
@@ -762,6 +767,65 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_kernel(const float* __restri
     }
 }
 
+// ROIPool backward with a fixed summation order (ptmi_roi_pool_bwd_det; rois grouped by image).  Owner computes: a WAVE owns one
+// (image, channel) plane, TILE cells of it at a time in LDS, and walks the image's ROIs in index order.  Lane b < P * P holds bin
+// b's (argmax, gradient); where several bins of the ROI name one cell, the lane of the lowest such bin adds them up in bin
+// order and is the only one to touch the cell.  A cell's value is therefore ((0 + roi r0's bins in order) + roi r1's ...): a
+// function of the inputs alone.  No atomics, no barrier across waves, every cell of dfeat written exactly once.
+constexpr int RPD_WAVES = 4;
+
+__global__ __launch_bounds__(64 * RPD_WAVES) void roi_pool_bwd_det_kernel(const float* __restrict__ dout, const int32_t* __restrict__ argmax,
+                                                                         const int32_t* __restrict__ img_off, float* __restrict__ dfeat,
+                                                                         int NC, int C, int HW, int PP, int TILE, int R)
+{
+    extern __shared__ float smem[];                              // RPD_WAVES x (TILE cells | 64 argmax | 64 gradients)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int plane_id = blockIdx.x * RPD_WAVES + wave;
+    if (plane_id >= NC) return;                                  // (no workgroup barrier below)
+    float* cells = smem + (size_t)wave * (TILE + 128);
+    int* am_s = reinterpret_cast<int*>(cells + TILE);
+    float* g_s = cells + TILE + 64;
+    const int n = plane_id / C, c = plane_id - n * C;
+    const int r0 = max(img_off[n], 0), r1 = min(img_off[n + 1], R);   // (offsets past the rows read nothing)
+    float* out = dfeat + (size_t)plane_id * HW;
+    const int chunks = (PP + 63) / 64;                           // bins beyond 64 go in further chunks, still in bin order
+    for (int t0 = 0; t0 < HW; t0 += TILE) {
+        const int tn = min(TILE, HW - t0);
+        for (int i = lane; i < tn; i += 64) cells[i] = 0.f;
+        __builtin_amdgcn_wave_barrier();
+        for (int r = r0; r < r1; ++r) {
+            const size_t base = ((size_t)r * C + c) * PP;
+            for (int k = 0; k < chunks; ++k) {
+                const int b = k * 64 + lane;
+                int am = -1;
+                float g = 0.f;
+                if (b < PP) {
+                    am = argmax[base + b] - t0;
+                    g = dout[base + b];
+                }
+                if (am < 0 || am >= tn) am = -1;
+                if (__ballot(am >= 0) == 0ull) continue;         // wave-uniform: the ROI has no bin in this tile
+                am_s[lane] = am;
+                g_s[lane] = g;
+                __builtin_amdgcn_wave_barrier();
+                bool leader = am >= 0;
+                float sum = 0.f;
+                const int nb = min(64, PP - k * 64);
+                for (int q = 0; q < nb; ++q) {
+                    if (am >= 0 && am_s[q] == am) {
+                        if (q < lane) leader = false;
+                        sum += g_s[q];
+                    }
+                }
+                if (leader) cells[am] += sum;
+                __builtin_amdgcn_wave_barrier();                 // the next chunk / ROI overwrites the strip and reads the cells
+            }
+        }
+        for (int i = lane; i < tn; i += 64) out[t0 + i] = cells[i];
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -843,7 +907,7 @@ int64_t ptmi_roi_align_bwd_ws_bytes(int r, int h, int w)
 int ptmi_roi_align_bwd_grouped(const float* dout, const float* rois, const int32_t* img_offsets, float* dfeat, void* ws,
                                int n, int c, int h, int w, int r, int pooled, float scale, ptmi_stream_t s)
 {
-    return roi_bwd_grouped(dout, rois, img_offsets, dfeat, ws, n, c, h, w, r, pooled, scale, (hipStream_t)s);
+    return roi_bwd_grouped(false, dout, rois, img_offsets, dfeat, ws, n, c, h, w, r, pooled, scale, (hipStream_t)s);
 }
 
 int ptmi_roi_align_bwd_grouped_ex(const float* dout, const float* rois, const int32_t* img_offsets, float* dfeat, void* ws,
@@ -851,7 +915,7 @@ int ptmi_roi_align_bwd_grouped_ex(const float* dout, const float* rois, const in
                                   int sampling_ratio)
 {
     ROI_VARIANT_ARGS("roi_align_bwd_grouped_ex");
-    return roi_bwd_grouped(dout, rois, img_offsets, dfeat, ws, n, c, h, w, r, pooled, scale, (hipStream_t)s, v);
+    return roi_bwd_grouped(false, dout, rois, img_offsets, dfeat, ws, n, c, h, w, r, pooled, scale, (hipStream_t)s, v);
 }
 
 int ptmi_roi_pool_fwd(const float* feat, const float* rois, float* out, int32_t* argmax, int n, int c, int h, int w, int r,
@@ -877,6 +941,36 @@ int ptmi_roi_pool_bwd(const float* dout, const int32_t* argmax, const float* roi
     hipLaunchKernelGGL(roi_pool_bwd_kernel, dim3(r), dim3(256), 0, (hipStream_t)s, dout, argmax, rois, dfeat, n, c, h * w,
                        pooled * pooled);
     PTMI_LAUNCH_CHECK("roi_pool_bwd");
+    return 0;
+}
+
+int ptmi_roi_align_bwd_det(const float* dout, const float* rois, const int32_t* img_offsets, float* dfeat, void* ws, int n, int c,
+                           int h, int w, int r, int pooled, float scale, ptmi_stream_t s, int aligned, int sampling_ratio)
+{
+    ROI_VARIANT_ARGS("roi_align_bwd_det");
+    PTMI_CHECK_ARG(ws, "roi_align_bwd_det: needs the ptmi_roi_align_bwd_ws_bytes workspace");
+    // ROIAlignV2 with the adaptive grid keeps its own table kernel (the instructions of ptmi_roi_align_bwd_grouped)
+    if (aligned == 1 && sampling_ratio == 0)
+        return roi_bwd_grouped(true, dout, rois, img_offsets, dfeat, ws, n, c, h, w, r, pooled, scale, (hipStream_t)s);
+    return roi_bwd_grouped(true, dout, rois, img_offsets, dfeat, ws, n, c, h, w, r, pooled, scale, (hipStream_t)s, v);
+}
+
+int ptmi_roi_pool_bwd_det(const float* dout, const int32_t* argmax, const int32_t* img_offsets, float* dfeat, int n, int c, int h,
+                          int w, int r, int pooled, ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(dfeat && img_offsets && n > 0 && c > 0 && h > 0 && w > 0 && r >= 0 && pooled > 0, "roi_pool_bwd_det: bad args");
+    PTMI_CHECK_ARG(r == 0 || (dout && argmax), "roi_pool_bwd_det: null buffer");
+    const int hw = h * w;
+    const int tile = hw < 8192 ? hw : 8192;                      // cells of a plane held in LDS at a time (32 KB a wave at most)
+    const size_t lds = (size_t)RPD_WAVES * (tile + 128) * sizeof(float);
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)roi_pool_bwd_det_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr = true;
+    }
+    hipLaunchKernelGGL(roi_pool_bwd_det_kernel, dim3(cdiv(n * c, RPD_WAVES)), dim3(64 * RPD_WAVES), lds, (hipStream_t)s, dout, argmax,
+                       img_offsets, dfeat, n * c, c, hw, pooled * pooled, tile, r);
+    PTMI_LAUNCH_CHECK("roi_pool_bwd_det");
     return 0;
 }
 

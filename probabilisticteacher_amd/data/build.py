@@ -14,6 +14,7 @@ from typing import Iterable, Iterator, List, Optional
 import torch
 import torch.distributed as dist
 
+from ..seeding import loader_seed
 from ..structures import Boxes, FreeInstances
 from . import datasets, prefetch
 from .augment import resize_batch, resize_shortest_edge_size
@@ -90,9 +91,12 @@ def _closing(it, ahead):
         ahead.close()
 
 
-def build_detection_semisup_train_loader_two_crops(cfg, mapper: Optional[DeviceTwoCropMapper] = None, seed: int = 0):
-    """build.py:107-217: yields (label_strong, label_weak, unlabel_strong, unlabel_weak) lists of records forever"""
+def build_detection_semisup_train_loader_two_crops(cfg, mapper: Optional[DeviceTwoCropMapper] = None, seed: Optional[int] = None):
+    """build.py:107-217: yields (label_strong, label_weak, unlabel_strong, unlabel_weak) lists of records forever.
+    seed None: cfg.SEED when it is >= 0, else 0.  The index streams use the value itself on every rank (they are sharded by
+    rank), the mapper adds its per-rank offset."""
     rank, world = _rank_world()
+    seed = loader_seed(cfg, seed)
     bl, bu = cfg.SOLVER.IMG_PER_BATCH_LABEL, cfg.SOLVER.IMG_PER_BATCH_UNLABEL
     assert bl > 0 and bl % world == 0, f"Total label batch size ({bl}) must be divisible by the number of gpus ({world})."
     assert bu > 0 and bu % world == 0, f"Total unlabel batch size ({bu}) must be divisible by the number of gpus ({world})."

@@ -12,8 +12,8 @@ from typing import Callable, Dict, List, Optional
 import torch
 import torch.distributed as dist
 
-from .. import ops
-from ..modeling import EnsembleTSModel, build_model
+from .. import ops, seeding
+from ..modeling import EnsembleTSModel, build_model, sampling
 from ..structures import Boxes, FreeInstances
 from ..solver import check_optimizer_options, lr_at
 from .flat import BucketedGradReducer, FlatParams, broadcast_
@@ -26,11 +26,14 @@ class PTrainer:
         return 2 if amp else 3
 
     def __init__(self, cfg, data_loader=None, ratio_fn: Optional[Callable[[], float]] = None,
-                 force_grad_reducer: bool = False, grad_reduce: str = "all_reduce"):
+                 force_grad_reducer: bool = False, grad_reduce: str = "all_reduce", deterministic: Optional[bool] = None):
         """force_grad_reducer: run the bucketed gradient all-reduce (hooks + collectives) even with one rank -- needs an
         initialised process group; the sum over one rank is the identity (single-GPU validation of the DDP path).
-        grad_reduce: "all_reduce" or "reduce_scatter" (engine/flat.py: BucketedGradReducer)."""
+        grad_reduce: "all_reduce" or "reduce_scatter" (engine/flat.py: BucketedGradReducer).
+        deterministic: run the step on the order-independent backward kernels (ops.deterministic), the static tile schedule and
+        one weight-gradient wave, so that same binary + same GPU model + same world size give the same bits; None = cfg.SEED >= 0."""
         self.cfg = cfg
+        self.deterministic = cfg.SEED >= 0 if deterministic is None else bool(deterministic)
         check_optimizer_options(cfg)
         # reference trainer.py:98 (cfg.SOLVER.AMP.ENABLED): mixed precision for the conv / FC GEMMs (see ops.py).  The mode
         # belongs to THIS trainer and is applied around each of its steps (ops.operand_rounding): "bf16", None, or -- for
@@ -58,18 +61,33 @@ class PTrainer:
         # static walk / one workgroup per CU is 0.5 - 3 % faster.  Waves chosen by profiles/r06_contention_waves_1_to_4.txt /
         # r06_contention_amp_waves_1_to_4.txt: fp32 3 (+1.4 % without contention, x1.13 with 8 CUs held; 4 costs +2.5 % for x1.10),
         # bf16-storage kernels 2 (+1.2 %, and no worse under contention than 3 or 4)
-        ops.set_tile_schedule("dynamic" if self.reducer.active else "static")
-        ops.set_wgrad_waves(self.ddp_wgrad_waves(bool(cfg.SOLVER.AMP.ENABLED)) if self.reducer.active else 1)
-        ops.set_p8_conv_waves(16 if self.reducer.active else 1)       # (SOLVER.AMP.ENABLED: the bf16-storage convolution, persistent too)
+        # A deterministic trainer keeps the single-GPU choices under the exchange as well: no kernel of either choice adds floats
+        # atomically, but only the static walk and the one-wave split have been checked bit for bit
+        shares_cus = self.reducer.active and not self.deterministic
+        ops.set_tile_schedule("dynamic" if shares_cus else "static")
+        ops.set_wgrad_waves(self.ddp_wgrad_waves(bool(cfg.SOLVER.AMP.ENABLED)) if shares_cus else 1)
+        ops.set_p8_conv_waves(16 if shares_cus else 1)       # (SOLVER.AMP.ENABLED: the bf16-storage convolution, persistent too)
         self._first_step = True
         self.joint_student_pass = True      # one backbone pass for the two student branches when they share a canvas
         self.ensem_ts_model = EnsembleTSModel(self.model_teacher, self.model)
         self.iter = self.start_iter = 0
         self.max_iter = cfg.SOLVER.MAX_ITER
         self._data_iter = iter(data_loader) if data_loader is not None else None
-        self._ratio_fn = ratio_fn or (lambda: random.uniform(0.5, 1.0))
+        # SEED >= 0: the trainer owns its generators, derived from (SEED, rank) -- a random.Random for the shrink-paste ratio and
+        # a device generator for the label-sampling keys (modeling/sampling.py) -- so two trainers built from one config draw the
+        # same numbers whatever else the process does.  SEED -1: the process globals, as before.
+        self._rng, self._key_gen = None, None
+        if cfg.SEED >= 0:
+            rank = dist.get_rank() if self.world_size > 1 else 0
+            self._rng = random.Random(seeding.derive(cfg.SEED, rank, seeding.STREAM_RATIO))
+            self._key_gen = torch.Generator(device=self.model.device)
+            self._key_gen.manual_seed(seeding.derive(cfg.SEED, rank, seeding.STREAM_KEYS))
+        self._ratio_fn = ratio_fn or (self._seeded_ratio if self._rng is not None else (lambda: random.uniform(0.5, 1.0)))
         self.last_metrics: Dict[str, float] = {}
         self._mean_int = [int(m) for m in cfg.MODEL.PIXEL_MEAN]     # pixel_mean.cpu().int() (trainer.py:569)
+
+    def _seeded_ratio(self) -> float:
+        return self._rng.uniform(0.5, 1.0)
 
     # ------------------------------------------------------------------ pseudo-labelling (trainer.py:179-257)
     def threshold_bbox(self, inst, proposal_type="roih"):
@@ -163,7 +181,8 @@ class PTrainer:
 
     # ------------------------------------------------------------------ the step (trainer.py:263-392)
     def run_step(self, data=None) -> Dict[str, float]:
-        with ops.operand_rounding(self.operand_rounding):
+        with ops.operand_rounding(self.operand_rounding), ops.deterministic(self.deterministic), \
+                sampling.key_generator(self._key_gen):
             return self._run_step(data)
 
     def _run_step(self, data=None) -> Dict[str, float]:

@@ -48,7 +48,8 @@ class ROIPooler(nn.Module):
         self.pooler_type, self.sampling_ratio = pooler_type, int(sampling_ratio)
         # the operator is resolved once (as box_regression.uncertainty_losses does for the loss pair)
         if pooler_type == "ROIPool":
-            self._pool = lambda feat, rois, img_offsets: ops.roi_pool(feat, rois, self.output_size, self.scale)
+            self._pool = lambda feat, rois, img_offsets: ops.roi_pool(feat, rois, self.output_size, self.scale,
+                                                                      img_offsets=img_offsets)
         else:
             aligned = pooler_type == "ROIAlignV2"
             self._pool = lambda feat, rois, img_offsets: ops.roi_align(feat, rois, self.output_size, self.scale, img_offsets,

@@ -11,6 +11,7 @@ The only injection point is the key source (`set_key_source`), the counterpart o
 parity tests hand in keys that encode a given sequence of permutations (`perm_key_source` below for the permutations recorded
 from the real reference, `keyed_perm_source` for a shared keyed stream), so the golden fixtures and the oracle comparisons
 run through exactly this code."""
+import contextlib
 from typing import Callable, List, Optional
 
 import torch
@@ -23,7 +24,7 @@ NOT_A_CANDIDATE = 2.0          # keys are in [0, 1)
 
 
 def set_key_source(fn: Optional[KeySource]) -> None:
-    """None = torch.rand on the device (production)."""
+    """None = torch.rand on the device (production; from the generator of `key_generator` if one is in scope)."""
     global _KEY_SOURCE
     _KEY_SOURCE = fn
 
@@ -59,11 +60,29 @@ def keyed_perm_source(kp) -> KeySource:
     return src
 
 
+_KEY_GENERATOR: Optional[torch.Generator] = None
+
+
+@contextlib.contextmanager
+def key_generator(gen: Optional[torch.Generator]):
+    """Scope the generator of the production key source (None: the device's global generator).  A trainer with SEED >= 0 owns a
+    device generator and applies it around each of its steps; an injected key source (`set_key_source`) still comes first."""
+    global _KEY_GENERATOR
+    prev = _KEY_GENERATOR
+    _KEY_GENERATOR = gen
+    try:
+        yield
+    finally:
+        _KEY_GENERATOR = prev
+
+
 def draw_keys(labels: torch.Tensor, sizes: Optional[List[int]], bg_label: int) -> torch.Tensor:
     if _KEY_SOURCE is not None:
         keys = _KEY_SOURCE(labels, sizes, bg_label).to(device=labels.device, dtype=torch.float32)
         assert keys.shape == labels.shape
         return keys
+    if _KEY_GENERATOR is not None:
+        return torch.rand(labels.shape, device=labels.device, generator=_KEY_GENERATOR)
     return torch.rand(labels.shape, device=labels.device)
 
 

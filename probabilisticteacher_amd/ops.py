@@ -143,6 +143,30 @@ def operand_rounding(mode: Optional[str]):
         set_operand_rounding(prev)
 
 
+# ============================================================================ order-independent backward (SEED >= 0)
+# The two backward kernels that add floats with hardware atomics -- the ROI pooler's scatter and get_deltas' gradient into the
+# source boxes -- have atomic-free counterparts with a fixed summation order (ptmi_roi_align_bwd_det / ptmi_roi_pool_bwd_det /
+# ptmi_get_deltas_bwd_src_det).  The flag routes the autograd backwards below to them; like the operand rounding it belongs to
+# a trainer, which applies it around each of its steps.
+_DETERMINISTIC = False
+
+
+def is_deterministic() -> bool:
+    return _DETERMINISTIC
+
+
+@contextlib.contextmanager
+def deterministic(flag: bool = True):
+    """Scope the order-independent backward kernels (see above); restores the previous setting on exit."""
+    global _DETERMINISTIC
+    prev = _DETERMINISTIC
+    _DETERMINISTIC = bool(flag)
+    try:
+        yield
+    finally:
+        _DETERMINISTIC = prev
+
+
 def _rnd(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     if _OPERAND_ROUNDING != "bf16_emulate" or t is None:
         return t
@@ -803,7 +827,9 @@ class _ROIAlign(torch.autograd.Function):
         rois, img_offsets = ctx.saved_tensors
         n, c, h, w, pooled, scale, aligned, sampling_ratio = ctx.meta
         dout = _chk(dout.contiguous())
-        if img_offsets is not None:
+        if _DETERMINISTIC:
+            dfeat = roi_align_bwd_det(dout, rois, img_offsets, n, c, h, w, pooled, scale, aligned, sampling_ratio)
+        elif img_offsets is not None:
             # rois grouped by image: LDS-accumulating kernel, no global atomics, writes every element of dfeat
             dfeat = roi_align_bwd_grouped(dout, rois, img_offsets, n, c, h, w, pooled, scale, aligned, sampling_ratio)
         else:
@@ -815,9 +841,53 @@ class _ROIAlign(torch.autograd.Function):
         return dfeat, None, None, None, None, None, None
 
 
+def _group_by_image(rois: torch.Tensor, n: int):
+    """(row order, img_offsets) that group the rows of rois by image index, rows of one image in their given order (a stable sort:
+    a function of rois alone); rows naming no image fall outside every group.  No host sync."""
+    img = rois[:, 0].to(torch.int32)
+    img_sorted, order = torch.sort(img, stable=True)
+    offsets = torch.searchsorted(img_sorted, torch.arange(n + 1, dtype=torch.int32, device=rois.device)).to(torch.int32)
+    return order, offsets
+
+
+def roi_align_bwd_det(dout: torch.Tensor, rois: torch.Tensor, img_offsets: Optional[torch.Tensor], n: int, c: int, h: int, w: int,
+                      pooled: int, scale: float, aligned=True, sampling_ratio: int = 0) -> torch.Tensor:
+    """roi_align_bwd_grouped through ptmi_roi_align_bwd_det: the atomic-free kernel or an error, never the atomic scatter.  Rows
+    not grouped by image (img_offsets None) are grouped here first."""
+    aligned, sampling_ratio = _roi_variant(aligned, sampling_ratio)
+    dout = _chk(dout.contiguous())
+    rois = _chk(rois.contiguous())
+    if img_offsets is None:
+        order, img_offsets = _group_by_image(rois, n)
+        rois, dout = rois[order].contiguous(), dout[order].contiguous()
+    dfeat = torch.empty((n, c, h, w), dtype=F32, device=dout.device)
+    with _prof("roi_align_bwd"):
+        ws = torch.empty(_lib.load().ptmi_roi_align_bwd_ws_bytes(rois.shape[0], h, w), dtype=torch.uint8, device=dout.device)
+        _lib.call("ptmi_roi_align_bwd_det", _ptr(dout), _ptr(rois), _ptr(_chk(img_offsets, torch.int32)), _ptr(dfeat), _ptr(ws),
+                  n, c, h, w, rois.shape[0], pooled, float(scale), _stream(), aligned, sampling_ratio)
+    return dfeat
+
+
+def roi_pool_bwd_det(dout: torch.Tensor, argmax: torch.Tensor, rois: torch.Tensor, img_offsets: Optional[torch.Tensor], n: int,
+                     c: int, h: int, w: int, pooled: int) -> torch.Tensor:
+    """ROIPool's feature-map gradient with a fixed summation order (ptmi_roi_pool_bwd_det)"""
+    dout = _chk(dout.contiguous())
+    argmax = _chk(argmax.contiguous(), torch.int32)
+    if img_offsets is None:
+        order, img_offsets = _group_by_image(_chk(rois.contiguous()), n)
+        dout, argmax = dout[order].contiguous(), argmax[order].contiguous()
+    dfeat = torch.empty((n, c, h, w), dtype=F32, device=dout.device)
+    with _prof("roi_pool_bwd"):
+        _lib.call("ptmi_roi_pool_bwd_det", _ptr(dout), _ptr(argmax), _ptr(_chk(img_offsets, torch.int32)), _ptr(dfeat), n, c, h, w,
+                  dout.shape[0], pooled, _stream())
+    return dfeat
+
+
 def roi_align_bwd_grouped(dout: torch.Tensor, rois: torch.Tensor, img_offsets: torch.Tensor, n: int, c: int, h: int, w: int,
                           pooled: int, scale: float, aligned=True, sampling_ratio: int = 0) -> torch.Tensor:
     """d(feature map) (n, c, h, w) from the gradient of ROIAlign's output (R, c * pooled * pooled) for rois grouped by image"""
+    if _DETERMINISTIC:
+        return roi_align_bwd_det(dout, rois, img_offsets, n, c, h, w, pooled, scale, aligned, sampling_ratio)
     aligned, sampling_ratio = _roi_variant(aligned, sampling_ratio)
     dout = _chk(dout.contiguous())
     dfeat = torch.empty((n, c, h, w), dtype=F32, device=dout.device)
@@ -862,11 +932,12 @@ def roi_align(feat, rois, pooled: int, scale: float, img_offsets=None, aligned=T
 # ============================================================================ ROIPool
 class _ROIPool(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, rois, pooled: int, scale: float):
+    def forward(ctx, feat, rois, pooled: int, scale: float, img_offsets=None):
         feat = _chk(feat.contiguous())
         rois = _chk(rois.contiguous())
         n, c, h, w = feat.shape
         r = rois.shape[0]
+        ctx.img_offsets = img_offsets
         out = torch.empty((r, c, pooled, pooled), dtype=F32, device=feat.device)
         argmax = torch.empty((r, c, pooled, pooled), dtype=torch.int32, device=feat.device)
         with _prof("roi_pool_fwd"):
@@ -882,18 +953,21 @@ class _ROIPool(torch.autograd.Function):
         rois, argmax = ctx.saved_tensors
         n, c, h, w, pooled = ctx.meta
         dout = _chk(dout.contiguous())
+        if _DETERMINISTIC:
+            return roi_pool_bwd_det(dout, argmax, rois, ctx.img_offsets, n, c, h, w, pooled), None, None, None, None
         dfeat = torch.empty((n, c, h, w), dtype=F32, device=dout.device)        # (zeroed by the entry point)
         with _prof("roi_pool_bwd"):
             _lib.call("ptmi_roi_pool_bwd", _ptr(dout), _ptr(argmax), _ptr(rois), _ptr(dfeat), n, c, h, w, rois.shape[0], pooled,
                       _stream())
-        return dfeat, None, None, None
+        return dfeat, None, None, None, None
 
 
-def roi_pool(feat, rois, pooled: int, scale: float, return_argmax: bool = False):
+def roi_pool(feat, rois, pooled: int, scale: float, return_argmax: bool = False, img_offsets=None):
     """torchvision roi_pool: the maximum over each bin's integer cells; rois (R,5) = [image index, x1, y1, x2, y2].  The int32
     argmax (flat h * W + w of the first maximum in raster order, -1 for an empty bin) is saved for the backward (an atomic
-    scatter: the feature-map gradient's summation order varies run to run) and returned on request."""
-    out, argmax = _ROIPool.apply(feat, rois, pooled, scale)
+    scatter: the feature-map gradient's summation order varies run to run; under ops.deterministic the owner-computes kernel,
+    which takes `img_offsets` if the rows are grouped by image and groups them itself otherwise) and returned on request."""
+    out, argmax = _ROIPool.apply(feat, rois, pooled, scale, img_offsets)
     return (out, argmax) if return_argmax else out
 
 
@@ -940,12 +1014,41 @@ class _GetDeltas(torch.autograd.Function):
         dsrc = None
         if ctx.needs_input_grad[0]:
             rows = src.shape[0]
+            if _DETERMINISTIC:          # row i is its own destination: the identity form of the fixed-order entry
+                return get_deltas_bwd_src_det(src, tgt, dd, None, rows, ctx.w), None, None, None, None, None
             dsrc = torch.zeros_like(src)
             if rows:
                 idx = torch.arange(rows, dtype=torch.int64, device=src.device)
                 _lib.call("ptmi_get_deltas_bwd_src", _ptr(src), _ptr(tgt), _ptr(_chk(dd.contiguous())), _ptr(idx), rows,
                           *ctx.w, _ptr(dsrc), _stream())
         return dsrc, None, None, None, None, None
+
+
+def get_deltas_bwd_src(src, tgt, ddeltas, src_index: torch.Tensor, n_dst: int, weights: Sequence[float]) -> torch.Tensor:
+    """d(loss)/d(source boxes) of get_deltas summed into (n_dst, 4) by src_index (int64, one destination per row).  Default: the
+    atomic scatter (ptmi_get_deltas_bwd_src); under ops.deterministic the fixed-order segmented reduction."""
+    if _DETERMINISTIC:
+        return get_deltas_bwd_src_det(src, tgt, ddeltas, src_index, n_dst, weights)
+    src, tgt, ddeltas = _chk(src.contiguous()), _chk(tgt.contiguous()), _chk(ddeltas.contiguous())
+    dsrc = torch.zeros((n_dst, 4), dtype=F32, device=src.device)
+    if src.shape[0]:
+        _lib.call("ptmi_get_deltas_bwd_src", _ptr(src), _ptr(tgt), _ptr(ddeltas), _ptr(_chk(src_index.contiguous(), torch.int64)),
+                  src.shape[0], *[float(v) for v in weights], _ptr(dsrc), _stream())
+    return dsrc
+
+
+def get_deltas_bwd_src_det(src, tgt, ddeltas, src_index: Optional[torch.Tensor], n_dst: int, weights: Sequence[float]) -> torch.Tensor:
+    """ptmi_get_deltas_bwd_src_det: src_index None = the identity (n_dst == rows)"""
+    src, tgt, ddeltas = _chk(src.contiguous()), _chk(tgt.contiguous()), _chk(ddeltas.contiguous())
+    rows = src.shape[0]
+    dsrc = torch.empty((n_dst, 4), dtype=F32, device=src.device)
+    ws = None
+    if src_index is not None:
+        src_index = _chk(src_index.contiguous(), torch.int64)
+        ws = _ws("get_deltas_det", 4 * _lib.load().ptmi_get_deltas_bwd_src_det_ws_floats(rows, n_dst), src.device)
+    _lib.call("ptmi_get_deltas_bwd_src_det", _ptr(src), _ptr(tgt), _ptr(ddeltas), _ptr(src_index), rows,
+              *[float(v) for v in weights], _ptr(dsrc), n_dst, _ptr(ws), _stream())
+    return dsrc
 
 
 def get_deltas(src, tgt, weights: Sequence[float]):

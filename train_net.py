@@ -27,7 +27,7 @@ def synthetic_loader(cfg, dev, rank, world):
     K = cfg.MODEL.ROI_HEADS.NUM_CLASSES
     bl, bu = cfg.SOLVER.IMG_PER_BATCH_LABEL // world, cfg.SOLVER.IMG_PER_BATCH_UNLABEL // world
     assert bl >= 1 and bu >= 1, "batch must be divisible by the world size (pt/data/build.py:174-187)"
-    gen = torch.Generator().manual_seed(1234 + rank * 1000)
+    gen = torch.Generator().manual_seed(1234 + rank * 1000 + (cfg.SEED if cfg.SEED >= 0 else 0))
     h, w = 800, 1333
     while True:
         yield (synth_records(gen, bl, h, w, K, dev), synth_records(gen, bl, h, w, K, dev),
@@ -61,7 +61,10 @@ def main():
         name, rest = spec.split("=", 1)
         dirname, split, classes = rest.split(":")
         datasets.register_pascal_voc(name, dirname, split, tuple(classes.split(",")))
-    torch.manual_seed(0)
+    from probabilisticteacher_amd.seeding import seed_all_rng
+    seed_all_rng(None if cfg.SEED < 0 else cfg.SEED + rank)    # D2 default_setup
+    if cfg.SEED < 0:
+        torch.manual_seed(0)                                   # (without a SEED the initial weights stay those of seed 0)
     if args.synthetic:
         loader = synthetic_loader(cfg, torch.device("cuda", local), rank, world)
     else:
