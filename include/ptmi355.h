@@ -535,6 +535,29 @@ int ptmi_clip_sgd_step(float* p, const float* g, float* buf, int64_t n, const fl
                        float clip_norm, float lr, float momentum, float weight_decay, int first,
                        ptmi_stream_t s);
 int ptmi_scale_by_clip(float* g, int64_t n, const float* sumsq, float clip_norm, ptmi_stream_t s);
+/* SOLVER.CLIP_GRADIENTS (D2 0.5 solver/build.py maybe_add_gradient_clipping, reached at trainer.py:80): torch's
+ * clip_grad_value_ / clip_grad_norm_ applied to every parameter on its own, i.e. to every SEGMENT of the flat buffers, after
+ * the global scale s above and before the update.  Device tables, built once by the caller:
+ *   seg_off   int64[S + 1]  ascending element offsets of the segments; segment i = [seg_off[i], seg_off[i + 1])
+ *   chunks    int64[C][2]   (start, segment): the segments cut into pieces of at most PTMI_SEG_CHUNK elements, segment by
+ *                           segment and ascending within one; a piece ends at start + PTMI_SEG_CHUNK or at its segment's end
+ *   seg_chunk int64[S + 1]  segment i owns chunks [seg_chunk[i], seg_chunk[i + 1])
+ * One workgroup per chunk.  A chunk whose descriptor does not lie inside its segment and inside [0, n) is skipped.
+ * n == 0 or S == 0: nothing is launched, 0 is returned. */
+#define PTMI_SEG_CHUNK 8192
+/* seg_norm[i] = || g s ||_2 (inf_norm 0) or max |g s| (inf_norm 1) over segment i.  No atomics, one fixed summation tree per
+ * chunk and per segment: the bits depend on the values and the tables only, not on the grid, the timing or the address of g.
+ * ws: C floats. */
+int ptmi_seg_gradnorm(const float* g, int64_t n, const int64_t* seg_off, const int64_t* seg_chunk, int S,
+                      const int64_t* chunks, int C, const float* sumsq, float clip_norm, int inf_norm, float* ws,
+                      float* seg_norm, ptmi_stream_t s);
+/* ptmi_clip_sgd_step with the per-segment clip: g' = clip(g*s) + wd*p, then as above; g is not written.
+ * clip_type 0 ("value"): clamp(g*s, -clip_value, clip_value), seg_norm unused (may be NULL).
+ * clip_type 1 ("norm"):  g*s*c, c = min(clip_value / (seg_norm[segment] + 1e-6), 1), seg_norm from ptmi_seg_gradnorm. */
+int ptmi_clip_sgd_step_seg(float* p, const float* g, float* buf, int64_t n, const int64_t* seg_off, int S,
+                           const int64_t* chunks, int C, const float* sumsq, float clip_norm, int clip_type,
+                           float clip_value, const float* seg_norm, float lr, float momentum, float weight_decay,
+                           int first, ptmi_stream_t s);
 
 /* ------------------------------------------------------------------ image prep (N18)
  * rcnn.py:40 -> D2 preprocess_image: out[i] (3,hmax,wmax) = (u8 - mean)/std, zero padded.

@@ -112,6 +112,8 @@ def _coerce(new, old, key):
         return list(new)
     if isinstance(old, float) and isinstance(new, int):
         return float(new)
+    if isinstance(old, float) and isinstance(new, str) and new.strip().lower().lstrip("+-") in ("inf", ".inf", "infinity"):
+        return float(new.strip().replace(".", ""))       # "inf" (YAML spells the float `.inf`; a bare `inf` arrives as a string)
     if isinstance(old, str) and new is None:
         return new
     raise ValueError(f"Type mismatch ({type(old)} vs. {type(new)}) for config key: {key}")
@@ -146,7 +148,13 @@ def _load_yaml_with_base(path: str) -> dict:
 
 
 def get_cfg() -> CfgNode:
-    """The detectron2==0.5 default values of every key the train step reads."""
+    """The detectron2==0.5 default values of every key the train step reads.
+
+    SOLVER.CLIP_GRADIENTS: detectron2 is not installed here; the defaults (ENABLED False, CLIP_TYPE "value", CLIP_VALUE 1.0,
+    NORM_TYPE 2.0) and the semantics are restated from D2 0.5's solver/build.py (`maybe_add_gradient_clipping`, which
+    `build_optimizer` wraps around torch.optim.SGD): with ENABLED, `optimizer.step()` first clips EVERY parameter's gradient on
+    its own -- CLIP_TYPE "value": torch.nn.utils.clip_grad_value_(p, CLIP_VALUE); "norm": clip_grad_norm_(p, CLIP_VALUE,
+    NORM_TYPE) -- and then updates.  solver.check_optimizer_options validates the values, engine/trainer.py applies them."""
     C = CfgNode()
     C.VERSION = 2
     C.OUTPUT_DIR = "./output"
@@ -162,7 +170,8 @@ def get_cfg() -> CfgNode:
         LR_SCHEDULER_NAME="WarmupMultiStepLR", MAX_ITER=40000, BASE_LR=0.001, MOMENTUM=0.9, NESTEROV=False,
         WEIGHT_DECAY=0.0001, WEIGHT_DECAY_NORM=0.0, GAMMA=0.1, STEPS=(30000,), WARMUP_FACTOR=1.0 / 1000,
         WARMUP_ITERS=1000, WARMUP_METHOD="linear", CHECKPOINT_PERIOD=5000, IMS_PER_BATCH=16, BIAS_LR_FACTOR=1.0,
-        WEIGHT_DECAY_BIAS=0.0001, AMP=dict(ENABLED=False)))
+        WEIGHT_DECAY_BIAS=0.0001, AMP=dict(ENABLED=False),
+        CLIP_GRADIENTS=dict(ENABLED=False, CLIP_TYPE="value", CLIP_VALUE=1.0, NORM_TYPE=2.0)))
     C.MODEL = CfgNode(dict(
         DEVICE="cuda", META_ARCHITECTURE="GeneralizedRCNN", MASK_ON=False, KEYPOINT_ON=False, LOAD_PROPOSALS=False,
         WEIGHTS="", PIXEL_MEAN=[103.530, 116.280, 123.675], PIXEL_STD=[1.0, 1.0, 1.0],

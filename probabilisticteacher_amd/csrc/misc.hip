@@ -3,6 +3,7 @@
 //   * image normalise + pad     (D2 preprocess_image reached at pt/modeling/meta_arch/rcnn.py:40)
 //   * shrink-and-paste resize   (pt/engine/trainer.py:557-590)
 //   * EMA / grad-norm / clip+SGD on flat parameter buffers (pt/engine/trainer.py:431-449,592-603,386)
+//   * per-parameter gradient clipping in that step        (D2 0.5 solver/build.py, reached at pt/engine/trainer.py:80)
 #include "common.h"
 
 namespace {
@@ -254,6 +255,177 @@ __global__ void scale_by_clip_kernel(float* __restrict__ g, int64_t n, const flo
         g[i] *= sc;
 }
 
+// ---- SOLVER.CLIP_GRADIENTS: per-parameter clipping on the flat buffers (D2 0.5 maybe_add_gradient_clipping) ----------
+// "Per parameter" = per segment of the flat buffer.  The host cuts every segment into chunks of at most PTMI_SEG_CHUNK
+// elements once (engine/flat.py); one workgroup per chunk, which reads its (start, segment) descriptor with scalar loads --
+// no per-element search, no launch per segment.  A descriptor that does not lie inside its segment is skipped.
+constexpr int SEG_CHUNK = PTMI_SEG_CHUNK;
+
+__device__ __forceinline__ bool seg_chunk_range(const int64_t* __restrict__ seg_off, int S,
+                                                const int64_t* __restrict__ chunks, int64_t n, int64_t& a, int64_t& e,
+                                                int& seg)
+{
+    a = chunks[2 * (int64_t)blockIdx.x];
+    const int64_t sg = chunks[2 * (int64_t)blockIdx.x + 1];
+    if (sg < 0 || sg >= S) return false;
+    seg = (int)sg;
+    if (a < 0 || a < seg_off[seg]) return false;
+    e = a + SEG_CHUNK;
+    if (e > seg_off[seg + 1]) e = seg_off[seg + 1];
+    if (e > n) e = n;
+    return a < e;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
+    return v;
+}
+
+// block_sum_256 / its max twin, by template flag; result valid in thread 0
+template <int INF>
+__device__ __forceinline__ float block_norm_reduce_256(float v, float* smem)
+{
+    if (!INF) return block_sum_256(v, smem);
+    v = wave_max(v);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) smem[wv] = v;
+    __syncthreads();
+    float r = 0.f;
+    if (threadIdx.x == 0) r = fmaxf(fmaxf(smem[0], smem[1]), fmaxf(smem[2], smem[3]));
+    __syncthreads();
+    return r;
+}
+
+template <int INF>
+__device__ __forceinline__ float norm_acc(float acc, float v)
+{
+    return INF ? fmaxf(acc, fabsf(v)) : acc + v * v;
+}
+
+// partial[chunk] = sum (g s)^2  or  max |g s|  over the chunk.  Element j of the chunk (counted from the chunk's start)
+// always goes to thread j % 256, accumulator (j / 256) % 4 while four rows are left and accumulator 0 after that, and the
+// accumulators, lanes and waves are combined in one fixed tree: the result is a function of the chunk's values alone -- not
+// of the grid, the timing or the buffer's address.  That is why the loads are one dword per lane (256 contiguous bytes per
+// wave instruction) instead of 16 B: a 16-B load would tie the lane <-> element assignment to the address (and behind a
+// learnable 18-float anchor table no segment starts on a 16-B boundary).
+template <int INF>
+__global__ __launch_bounds__(256) void seg_gradnorm_partial_kernel(const float* __restrict__ g, int64_t n,
+                                                                   const int64_t* __restrict__ seg_off, int S,
+                                                                   const int64_t* __restrict__ chunks,
+                                                                   const float* __restrict__ sumsq, float clip,
+                                                                   float* __restrict__ partial)
+{
+    __shared__ float sm[4];
+    int64_t a, e;
+    int seg;
+    if (!seg_chunk_range(seg_off, S, chunks, n, a, e, seg)) {
+        if (threadIdx.x == 0) partial[blockIdx.x] = 0.f;
+        return;
+    }
+    const float sc = clip / fmaxf(sqrtf(sumsq[0]), clip);
+    const float* gp = g + a;
+    const int len = (int)(e - a);
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int i = threadIdx.x;
+    for (; i + 768 < len; i += 1024) {
+        const float v0 = gp[i], v1 = gp[i + 256], v2 = gp[i + 512], v3 = gp[i + 768];
+        a0 = norm_acc<INF>(a0, v0 * sc);
+        a1 = norm_acc<INF>(a1, v1 * sc);
+        a2 = norm_acc<INF>(a2, v2 * sc);
+        a3 = norm_acc<INF>(a3, v3 * sc);
+    }
+    for (; i < len; i += 256) a0 = norm_acc<INF>(a0, gp[i] * sc);
+    const float acc = INF ? fmaxf(fmaxf(a0, a1), fmaxf(a2, a3)) : (a0 + a1) + (a2 + a3);
+    const float t = block_norm_reduce_256<INF>(acc, sm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+// seg_norm[s] = sqrt(sum of the segment's chunk partials) or their maximum: chunks ascending per thread, then the fixed tree.
+// A segment without chunks (a zero-sized parameter) gets 0.
+template <int INF>
+__global__ __launch_bounds__(256) void seg_gradnorm_final_kernel(const float* __restrict__ partial,
+                                                                 const int64_t* __restrict__ seg_chunk, int C,
+                                                                 float* __restrict__ seg_norm)
+{
+    __shared__ float sm[4];
+    int64_t c0 = seg_chunk[blockIdx.x], c1 = seg_chunk[blockIdx.x + 1];
+    if (c0 < 0) c0 = 0;
+    if (c1 > C) c1 = C;
+    float acc = 0.f;
+    for (int64_t c = c0 + threadIdx.x; c < c1; c += 256) acc = INF ? fmaxf(acc, partial[c]) : acc + partial[c];
+    const float t = block_norm_reduce_256<INF>(acc, sm);
+    if (threadIdx.x == 0) seg_norm[blockIdx.x] = INF ? t : sqrtf(t);
+}
+
+// clip_sgd_kernel's update with the per-parameter clip between the global scale and the weight decay.
+// NORM = 0: clamp(g s, -v, v) (NaN kept, as torch.clamp);  NORM = 1: g s c, c = min(v / (seg_norm + 1e-6), 1).
+template <int NORM>
+__device__ __forceinline__ void clip_sgd_seg_elem(float& pv, float gv, float& bv, float sc, float cv, float lr, float mu,
+                                                  float wd, int first)
+{
+    gv *= sc;
+    if (NORM) gv *= cv;
+    else gv = gv < -cv ? -cv : (gv > cv ? cv : gv);
+    gv = gv + wd * pv;
+    bv = first ? gv : mu * bv + gv;
+    pv = pv - lr * bv;
+}
+
+// g is read only.  16-B accesses where p, g and buf sit at the same offset within 16 B (a scalar head up to that boundary, a
+// scalar tail); one dword per lane otherwise.  Elementwise: the path changes no bit of the result.
+template <int NORM>
+__global__ __launch_bounds__(256) void clip_sgd_seg_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ buf, int64_t n,
+                                                           const int64_t* __restrict__ seg_off, int S,
+                                                           const int64_t* __restrict__ chunks,
+                                                           const float* __restrict__ sumsq, float clip, float clip_value,
+                                                           const float* __restrict__ seg_norm, float lr, float mu,
+                                                           float wd, int first)
+{
+    int64_t a, e;
+    int seg;
+    if (!seg_chunk_range(seg_off, S, chunks, n, a, e, seg)) return;
+    const float sc = clip / fmaxf(sqrtf(sumsq[0]), clip);
+    const float cv = NORM ? fminf(clip_value / (seg_norm[seg] + 1e-6f), 1.f) : clip_value;
+    float* pp = p + a;
+    const float* gp = g + a;
+    float* bp = buf + a;
+    const int len = (int)(e - a);
+    const uintptr_t ap = (uintptr_t)pp, ag = (uintptr_t)gp, ab = (uintptr_t)bp;
+    int head = len, nv = 0;
+    if ((((ap ^ ag) | (ap ^ ab)) & 15) == 0) {
+        head = (int)(((16 - (ap & 15)) & 15) >> 2);
+        if (head > len) head = len;
+        nv = (len - head) >> 2;
+    }
+    for (int i = threadIdx.x; i < head; i += 256) {
+        float pv = pp[i], bv = bp[i];
+        clip_sgd_seg_elem<NORM>(pv, gp[i], bv, sc, cv, lr, mu, wd, first);
+        bp[i] = bv;
+        pp[i] = pv;
+    }
+    float4* p4 = reinterpret_cast<float4*>(pp + head);
+    const float4* g4 = reinterpret_cast<const float4*>(gp + head);
+    float4* b4 = reinterpret_cast<float4*>(bp + head);
+    for (int i = threadIdx.x; i < nv; i += 256) {
+        float4 pv = p4[i], bv = b4[i];
+        const float4 gv = g4[i];
+        clip_sgd_seg_elem<NORM>(pv.x, gv.x, bv.x, sc, cv, lr, mu, wd, first);
+        clip_sgd_seg_elem<NORM>(pv.y, gv.y, bv.y, sc, cv, lr, mu, wd, first);
+        clip_sgd_seg_elem<NORM>(pv.z, gv.z, bv.z, sc, cv, lr, mu, wd, first);
+        clip_sgd_seg_elem<NORM>(pv.w, gv.w, bv.w, sc, cv, lr, mu, wd, first);
+        b4[i] = bv;
+        p4[i] = pv;
+    }
+    for (int i = head + 4 * nv + threadIdx.x; i < len; i += 256) {
+        float pv = pp[i], bv = bp[i];
+        clip_sgd_seg_elem<NORM>(pv, gp[i], bv, sc, cv, lr, mu, wd, first);
+        bp[i] = bv;
+        pp[i] = pv;
+    }
+}
+
 inline unsigned grid_for(int64_t n, int per = 256, int cap = 8192)
 {
     int64_t b = (n + per - 1) / per;
@@ -396,6 +568,50 @@ int ptmi_clip_sgd_step(float* p, const float* g, float* buf, int64_t n, const fl
     hipLaunchKernelGGL(clip_sgd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, p, g, buf, n, sumsq,
                        clip_norm, lr, momentum, weight_decay, first);
     PTMI_LAUNCH_CHECK("clip_sgd_step");
+    return 0;
+}
+
+int ptmi_seg_gradnorm(const float* g, int64_t n, const int64_t* seg_off, const int64_t* seg_chunk, int S,
+                      const int64_t* chunks, int C, const float* sumsq, float clip_norm, int inf_norm, float* ws,
+                      float* seg_norm, ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(n >= 0 && S >= 0 && C >= 0, "seg_gradnorm: negative length");
+    if (n == 0 || S == 0) return 0;
+    PTMI_CHECK_ARG(g && seg_off && seg_chunk && chunks && sumsq && ws && seg_norm && C > 0 && (inf_norm == 0 || inf_norm == 1),
+                   "seg_gradnorm: bad args");
+    if (inf_norm) {
+        hipLaunchKernelGGL(seg_gradnorm_partial_kernel<1>, dim3((unsigned)C), dim3(256), 0, (hipStream_t)s, g, n, seg_off, S,
+                           chunks, sumsq, clip_norm, ws);
+        PTMI_LAUNCH_CHECK("seg_gradnorm_partial");
+        hipLaunchKernelGGL(seg_gradnorm_final_kernel<1>, dim3((unsigned)S), dim3(256), 0, (hipStream_t)s, ws, seg_chunk, C,
+                           seg_norm);
+    } else {
+        hipLaunchKernelGGL(seg_gradnorm_partial_kernel<0>, dim3((unsigned)C), dim3(256), 0, (hipStream_t)s, g, n, seg_off, S,
+                           chunks, sumsq, clip_norm, ws);
+        PTMI_LAUNCH_CHECK("seg_gradnorm_partial");
+        hipLaunchKernelGGL(seg_gradnorm_final_kernel<0>, dim3((unsigned)S), dim3(256), 0, (hipStream_t)s, ws, seg_chunk, C,
+                           seg_norm);
+    }
+    PTMI_LAUNCH_CHECK("seg_gradnorm_final");
+    return 0;
+}
+
+int ptmi_clip_sgd_step_seg(float* p, const float* g, float* buf, int64_t n, const int64_t* seg_off, int S,
+                           const int64_t* chunks, int C, const float* sumsq, float clip_norm, int clip_type,
+                           float clip_value, const float* seg_norm, float lr, float momentum, float weight_decay,
+                           int first, ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(n >= 0 && S >= 0 && C >= 0, "clip_sgd_step_seg: negative length");
+    if (n == 0 || S == 0) return 0;
+    PTMI_CHECK_ARG(p && g && buf && seg_off && chunks && sumsq && C > 0 && (clip_type == 0 || (clip_type == 1 && seg_norm)) &&
+                   clip_value > 0.f, "clip_sgd_step_seg: bad args");
+    if (clip_type == 1)
+        hipLaunchKernelGGL(clip_sgd_seg_kernel<1>, dim3((unsigned)C), dim3(256), 0, (hipStream_t)s, p, g, buf, n, seg_off, S,
+                           chunks, sumsq, clip_norm, clip_value, seg_norm, lr, momentum, weight_decay, first);
+    else
+        hipLaunchKernelGGL(clip_sgd_seg_kernel<0>, dim3((unsigned)C), dim3(256), 0, (hipStream_t)s, p, g, buf, n, seg_off, S,
+                           chunks, sumsq, clip_norm, clip_value, seg_norm, lr, momentum, weight_decay, first);
+    PTMI_LAUNCH_CHECK("clip_sgd_step_seg");
     return 0;
 }
 

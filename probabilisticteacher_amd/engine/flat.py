@@ -70,6 +70,36 @@ class FlatParams:
         return self.flat[: self.n_trainable]
 
 
+def segment_offsets(fp: FlatParams) -> List[int]:
+    """The S + 1 element offsets of the trainable parameters in the flat buffers, in the order of `fp.index`: parameter i is
+    [off[i], off[i + 1]).  They are contiguous from 0 and end at `fp.n_trainable` (trainable parameters lead the buffer)."""
+    offs = [0]
+    for n, p in fp.params.items():
+        if not p.requires_grad:
+            continue
+        off, k = fp.index[n]
+        if off != offs[-1]:
+            raise ValueError(f"trainable parameter {n} starts at {off}, not behind its predecessor at {offs[-1]}")
+        offs.append(off + k)
+    if offs[-1] != fp.n_trainable:
+        raise ValueError(f"the trainable parameters end at {offs[-1]}, the flat buffer's trainable part at {fp.n_trainable}")
+    return offs
+
+
+def segment_chunks(offsets: List[int], chunk: int) -> Tuple[List[Tuple[int, int]], List[int]]:
+    """Cut the segments into pieces of at most `chunk` elements, one workgroup each in the per-parameter clipping kernels
+    (include/ptmi355.h): ([(start, segment), ...], first chunk of every segment + the chunk count).  An empty segment owns
+    no chunk."""
+    if chunk <= 0 or any(b < a for a, b in zip(offsets[:-1], offsets[1:])) or (offsets and offsets[0] < 0):
+        raise ValueError("segment offsets must ascend from a non-negative start, the chunk size must be positive")
+    chunks, first = [], []
+    for i, (a, b) in enumerate(zip(offsets[:-1], offsets[1:])):
+        first.append(len(chunks))
+        chunks.extend((s, i) for s in range(a, b, chunk))
+    first.append(len(chunks))
+    return chunks, first
+
+
 def allreduce_mean_(flat_grad: torch.Tensor, world_size: int, chunk_elems: int = 16 * 1024 * 1024, group=None):
     """Average `flat_grad` over ranks in place: DDP's gradient all-reduce (trainer.py:92-95,384) issued as a few
     large collectives over the flat buffer.  `backend="nccl"` is RCCL over xGMI on ROCm; gloo works for CPU tests."""

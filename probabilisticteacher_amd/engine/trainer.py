@@ -15,8 +15,8 @@ import torch.distributed as dist
 from .. import ops, seeding
 from ..modeling import EnsembleTSModel, build_model, sampling
 from ..structures import Boxes, FreeInstances
-from ..solver import check_optimizer_options, lr_at
-from .flat import BucketedGradReducer, FlatParams, broadcast_
+from ..solver import check_optimizer_options, clip_gradients_options, lr_at
+from .flat import BucketedGradReducer, FlatParams, broadcast_, segment_offsets
 
 
 class PTrainer:
@@ -52,6 +52,11 @@ class PTrainer:
         broadcast_(self.student.flat)                  # trainer.py:495 _sync_params_and_buffers
         broadcast_(self.teacher.flat)
         self.momentum_buf = torch.zeros_like(self.student.trainable())
+        # SOLVER.CLIP_GRADIENTS (D2 0.5 maybe_add_gradient_clipping): every parameter is a segment of the flat buffers; the
+        # device tables of the segment-aware step are built here, once
+        self._clip_gradients = clip_gradients_options(cfg)
+        self._segments = (ops.SegmentTable(segment_offsets(self.student), self.student.flat.device)
+                          if self._clip_gradients is not None else None)
         # gradient exchange overlapped with backward: 16 MB buckets from the tail of the flat buffer (box head first)
         self.reducer = BucketedGradReducer(self.student, self.world_size, bucket_elems=4 * 1024 * 1024,
                                            force=force_grad_reducer, mode=grad_reduce)
@@ -171,11 +176,21 @@ class PTrainer:
 
     @torch.no_grad()
     def _clip_and_step(self, clip_norm: float):
-        """trainer.py:385-386: clip_gradient(model, 10.) + optimizer.step() fused: one reduction + one update."""
+        """trainer.py:385-386: clip_gradient(model, 10.) + optimizer.step() fused: one reduction + one update.
+        SOLVER.CLIP_GRADIENTS.ENABLED: the optimiser the reference builds (D2 build_optimizer) clips every parameter's gradient
+        on its own inside step(), i.e. AFTER the global clip: "value" is a clamp inside the update, "norm" one more pass over g
+        for the per-segment norms.  The returned sum of squares (the grad_norm metric) is the global pre-clip one either way."""
         g = self.student.grad
         ss = ops.sumsq(g)
-        ops.clip_sgd_step(self.student.trainable(), g, self.momentum_buf, ss, clip_norm, lr_at(self.cfg, self.iter),
-                          self.cfg.SOLVER.MOMENTUM, self.cfg.SOLVER.WEIGHT_DECAY, self._first_step)
+        S = self.cfg.SOLVER
+        if self._clip_gradients is None:
+            ops.clip_sgd_step(self.student.trainable(), g, self.momentum_buf, ss, clip_norm, lr_at(self.cfg, self.iter),
+                              S.MOMENTUM, S.WEIGHT_DECAY, self._first_step)
+        else:
+            clip_type, clip_value, inf_norm = self._clip_gradients
+            norms = ops.seg_gradnorm(g, self._segments, ss, clip_norm, inf_norm) if clip_type == "norm" else None
+            ops.clip_sgd_step_seg(self.student.trainable(), g, self.momentum_buf, self._segments, ss, clip_norm, clip_type,
+                                  clip_value, norms, lr_at(self.cfg, self.iter), S.MOMENTUM, S.WEIGHT_DECAY, self._first_step)
         self._first_step = False
         return ss
 

@@ -1457,6 +1457,61 @@ def scale_by_clip(g, sumsq_t, clip_norm) -> None:
     _lib.call("ptmi_scale_by_clip", _ptr(_chk(g)), g.numel(), _ptr(sumsq_t), float(clip_norm), _stream())
 
 
+SEG_CHUNK = 8192       # PTMI_SEG_CHUNK of include/ptmi355.h
+
+
+class SegmentTable:
+    """Device tables of the per-parameter clipping kernels (include/ptmi355.h), built ONCE from the S + 1 host offsets of the
+    segments: one int64 tensor [seg_off (S + 1) | seg_chunk (S + 1) | chunks (C x 2)] and the two fp32 workspaces."""
+
+    def __init__(self, offsets: Sequence[int], device):
+        from .engine.flat import segment_chunks
+        offsets = [int(o) for o in offsets]
+        if len(offsets) < 1:
+            raise ValueError("a segment table needs at least the offset 0")
+        chunks, first = segment_chunks(offsets, SEG_CHUNK)
+        self.S, self.C, self.n = len(offsets) - 1, len(chunks), offsets[-1]
+        if offsets[0] != 0:
+            raise ValueError("the first segment must start at element 0 of the flat buffers")
+        words = offsets + first + [w for c in chunks for w in c]
+        self.table = torch.tensor(words, dtype=torch.int64).to(device)
+        self.seg_off, self.seg_chunk = self.table[: self.S + 1], self.table[self.S + 1: 2 * self.S + 2]
+        self.chunks = self.table[2 * self.S + 2:]
+        self.ws = torch.empty(max(self.C, 1), dtype=F32, device=device)
+        self.seg_norm = torch.empty(max(self.S, 1), dtype=F32, device=device)
+
+    def check(self, *flats):
+        for t in flats:
+            _chk(t)
+            if t.numel() != self.n or t.device != self.table.device:
+                raise ValueError(f"flat buffer of {t.numel()} elements on {t.device}: the segment table covers {self.n} on "
+                                 f"{self.table.device}")
+
+
+def seg_gradnorm(g, table: SegmentTable, sumsq_t, clip_norm, inf_norm: bool) -> torch.Tensor:
+    """Per-segment norm (L2, or max-abs) of g * clip_norm / max(sqrt(sumsq), clip_norm) into table.seg_norm[:S]."""
+    table.check(g)
+    _lib.call("ptmi_seg_gradnorm", _ptr(g), g.numel(), _ptr(table.seg_off), _ptr(table.seg_chunk), table.S,
+              _ptr(table.chunks), table.C, _ptr(sumsq_t), float(clip_norm), int(bool(inf_norm)), _ptr(table.ws),
+              _ptr(table.seg_norm), _stream())
+    return table.seg_norm[: table.S]
+
+
+def clip_sgd_step_seg(p, g, buf, table: SegmentTable, sumsq_t, clip_norm, clip_type: str, clip_value, seg_norm, lr, momentum,
+                      weight_decay, first: bool) -> None:
+    """clip_sgd_step with SOLVER.CLIP_GRADIENTS: clip_type "value" clamps g * s per element, "norm" scales every segment by
+    min(clip_value / (seg_norm + 1e-6), 1) with seg_norm from seg_gradnorm.  g is not written."""
+    if clip_type not in ("value", "norm"):
+        raise ValueError(f"unknown clip type {clip_type!r}")
+    if clip_type == "norm" and seg_norm is None:
+        raise ValueError("clip type 'norm' needs the segment norms of seg_gradnorm")
+    table.check(p, g, buf)
+    _lib.call("ptmi_clip_sgd_step_seg", _ptr(p), _ptr(g), _ptr(buf), p.numel(), _ptr(table.seg_off), table.S,
+              _ptr(table.chunks), table.C, _ptr(sumsq_t), float(clip_norm), int(clip_type == "norm"), float(clip_value),
+              _ptr(seg_norm) if clip_type == "norm" else None, float(lr), float(momentum), float(weight_decay), int(first),
+              _stream())
+
+
 def _image_desc(rows, device) -> torch.Tensor:
     """rows of 8 ints -> device int64 descriptor table (pinned staging, async copy: no stream synchronisation)."""
     return torch.tensor(rows, dtype=torch.int64).pin_memory().to(device, non_blocking=True)

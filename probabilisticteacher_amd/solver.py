@@ -51,7 +51,32 @@ def check_optimizer_options(cfg) -> None:
         raise ValueError("SOLVER.BIAS_LR_FACTOR != 1 is not implemented by the fused clip+SGD step")
     if float(S.WEIGHT_DECAY_BIAS) != float(S.WEIGHT_DECAY):
         raise ValueError("SOLVER.WEIGHT_DECAY_BIAS != SOLVER.WEIGHT_DECAY is not implemented by the fused clip+SGD step")
+    clip_gradients_options(cfg)
     lr_at(cfg, 0)          # unknown scheduler / warm-up names raise here, before the first step
+
+
+def clip_gradients_options(cfg):
+    """SOLVER.CLIP_GRADIENTS as the fused step takes it: None when disabled (D2 0.5 does not look at the other three keys
+    then), else (clip_type "value" | "norm", clip_value > 0, inf_norm).  D2 accepts any NORM_TYPE torch does; the segment-norm
+    kernel implements 2.0 and inf (float, or the string "inf" a YAML file or a command-line override delivers)."""
+    G = cfg.SOLVER.CLIP_GRADIENTS
+    if not G.ENABLED:
+        return None
+    if G.CLIP_TYPE not in ("value", "norm"):
+        raise ValueError(f"SOLVER.CLIP_GRADIENTS.CLIP_TYPE must be 'value' or 'norm' (per-parameter clipping), got {G.CLIP_TYPE!r}")
+    try:
+        value = float(G.CLIP_VALUE)
+    except (TypeError, ValueError):
+        value = float("nan")
+    if not value > 0.0:
+        raise ValueError(f"SOLVER.CLIP_GRADIENTS.CLIP_VALUE must be > 0, got {G.CLIP_VALUE!r}")
+    try:
+        norm_type = float(G.NORM_TYPE)
+    except (TypeError, ValueError):
+        norm_type = float("nan")
+    if norm_type not in (2.0, math.inf):
+        raise ValueError(f"SOLVER.CLIP_GRADIENTS.NORM_TYPE must be 2.0 or inf, got {G.NORM_TYPE!r}")
+    return G.CLIP_TYPE, value, norm_type == math.inf
 
 
 def scheduler_state(cfg, last_iter: int, n_groups: int = 1) -> dict:
