@@ -34,8 +34,9 @@ def _deps_mtime():
 def _compile(src):
     obj = os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
     path = os.path.join(CSRC, src)
-    hdr_m = max(os.path.getmtime(os.path.join(CSRC, "common.h")),
-                os.path.getmtime(os.path.join(HERE, "..", "include", "ptmi355.h")))
+    # every header counts for every object: no per-file dependency lists to keep right
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdr_m = max(os.path.getmtime(p) for p in hdrs + [os.path.join(HERE, "..", "include", "ptmi355.h")])
     if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(path), hdr_m):
         return obj
     cmd = ["hipcc"] + FLAGS + FILE_FLAGS.get(src, []) + (["-x", "hip"] if src.endswith(".cpp") else []) + ["-c", path, "-o", obj]

@@ -1,8 +1,7 @@
-// abi.cpp -- error reporting + version of libptmi355.so.
+// abi.cpp -- error reporting, the per-device CU count + version of libptmi355.so.
 #include <stdarg.h>
-#include <stdio.h>
 
-#include "../../include/ptmi355.h"
+#include "common.h"
 
 static thread_local char g_err[512] = "";
 
@@ -12,6 +11,19 @@ void ptmi_set_error(const char* fmt, ...)
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+// a launch asks per call (35 convolutions per step); a benign race at worst writes the same value twice
+int ptmi_device_cus()
+{
+    static int cus_by_dev[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    if (dev >= 0 && dev < 64 && cus_by_dev[dev] > 0) return cus_by_dev[dev];
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
+    if (dev >= 0 && dev < 64) cus_by_dev[dev] = cus;
+    return cus;
 }
 
 extern "C" {

@@ -519,7 +519,6 @@ __global__ void fill_nomatch_kernel(int64_t* __restrict__ midx, int8_t* __restri
 }
 
 // ---------------------------------------------------------------------------------- RPN prepare
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 __global__ void rpn_prepare_kernel(const float* __restrict__ decoded, const float* __restrict__ slog,
                                    const int32_t* __restrict__ sidx, const float* __restrict__ sigma,

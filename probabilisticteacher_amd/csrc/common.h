@@ -8,6 +8,10 @@
 
 void ptmi_set_error(const char* fmt, ...);
 
+// CUs of the current device (abi.cpp): a hardware constant, looked up once per device id and cached; 256 if the runtime
+// cannot tell.  Internal to the library: not part of the C ABI.
+__attribute__((visibility("hidden"))) int ptmi_device_cus();
+
 #define PTMI_CHECK_ARG(cond, ...)            \
     do {                                     \
         if (!(cond)) {                       \
@@ -29,6 +33,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 ptmi_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 ptmi_bf16x4 __attribute__((ext_vector_type(4)));
+
+// v_mfma_f32_32x32x2_f32: fp32 in, fp32 accumulate (conv.hip, gemm.hip)
+__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---- buffer -> LDS DMA helpers (buffer_load_dword[x4] ... lds) ----------------------------------------------
 // Raw buffer resource over [base, base + bytes): lanes whose offset is >= bytes (e.g. 0xFFFFFFFF) are zero-filled

@@ -23,10 +23,6 @@ namespace {
 
 constexpr int TW = 32;   // output pixels per MFMA column block
 
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
 // ------------------------------------------------------------------------------------ forward, buffer-DMA pipeline
 // Default forward / dgrad kernel: K walked in 4-channel chunks, double-buffered LDS, ONE workgroup barrier per chunk,
 // 72 MFMAs per wave per chunk:   issue DMA(chunk c+1 -> buf^1) ; MFMAs on buf ; s_waitcnt vmcnt(0) ; s_barrier.

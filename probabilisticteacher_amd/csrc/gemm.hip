@@ -14,9 +14,6 @@ namespace {
 
 constexpr int BMN = 128;
 
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
 // bf16-input / fp32-accumulate variant (SOLVER.AMP.ENABLED, BASELINE configs[4]): the operands stay fp32 in HBM and
 // LDS; a lane rounds its eight k values to bf16 (v_cvt_pk_bf16_f32, round-to-nearest-even) on the way from LDS to the
 // MFMA: v_mfma_f32_32x32x16_bf16, lane half h element j <-> the same k for A and B.

@@ -22,8 +22,6 @@ constexpr int WS_SUM = 0, WS_CNT = 1024, WS_SCALE = 2048;
 constexpr float PI_F = 3.14159265358979323846f;
 constexpr float E_F = 2.71828182845904523536f;
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 inline int blocks_for(int64_t n)
 {
     int64_t b = (n + 255) / 256;

@@ -974,9 +974,7 @@ int ptmi_p8_conv3x3_waves(const void* x, const void* wp, const float* bias, cons
     const int64_t nWork = cdiv64(nPix, 8) * 8 * coTiles;                // work items (some beyond nPix: skipped by the kernel)
     PTMI_CHECK_ARG(nWork < (1ll << 31), "p8_conv3x3: too many tiles");
     // persistent workgroups: one per CU (a multiple of 8: a work item stays on the XCD of its id mod 8)
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-        cus = 256;
+    const int cus = ptmi_device_cus();
     // waves > 1: that many fills of the one-workgroup-per-CU slots, each workgroup walking a 1 / waves share of the items (still a
     // multiple of 8: the XCD affinity of an item id stays) -- the hardware dispatcher then hands the later workgroups to whichever
     // CU frees up first, so CUs held by another kernel (a collective overlapping backward) cost their share, not a second pass

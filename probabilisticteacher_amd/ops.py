@@ -202,28 +202,16 @@ def conv3x3_wgrad(x: torch.Tensor, dz: torch.Tensor, cout: int):
     n, cin, h, w = x.shape
     dw = torch.empty(cout, cin, 3, 3, dtype=F32, device=x.device)
     db = torch.empty(cout, dtype=F32, device=x.device)
-    lib = _lib.load()
-    kind = _wgrad_kind(cin, cout, h, w)
-    if kind == "wino4w":
-        # round 5: the F(4x4,3x3)-domain kernel (csrc/wino4w.hip; workgroup = 64 co x 32 ci)
-        ws = _ws("wgrad", lib.ptmi_conv3x3_wino4_wgrad_ws_floats_waves(n, cin, cout, h, w, _WGRAD_WAVES) * 4, x.device)
-        with _prof("conv3x3_wino4_wgrad", 2.0 * 9 * cin * cout * h * w * n, issued=wino4_wgrad_issued_flops(n, cin, cout, h, w)):
-            _lib.call("ptmi_conv3x3_wino4_wgrad_waves", _ptr(x), _ptr(dz), _ptr(dw), _ptr(db), _ptr(ws), n, cin, cout, h, w, 0,
-                      _WGRAD_WAVES, _stream())
-    elif kind == "wino":
-        ws = _ws("wgrad", lib.ptmi_conv3x3_wino_wgrad_ws_floats_waves(n, cin, cout, h, w, _WGRAD_WAVES) * 4, x.device)
-        with _prof("conv3x3_wino_wgrad", 2.0 * 9 * cin * cout * h * w * n, issued=wino_wgrad_issued_flops(n, cin, cout, h, w)):
-            _lib.call("ptmi_conv3x3_wino_wgrad_waves", _ptr(x), _ptr(dz), _ptr(dw), _ptr(db), _ptr(ws), n, cin, cout, h, w, 0,
-                      _WGRAD_WAVES, _stream())
-    else:
-        ws = _ws("wgrad", lib.ptmi_conv3x3_wgrad_ws_floats(n, cin, cout, h, w) * 4, x.device)
-        with _prof("conv3x3_wgrad", 2.0 * 9 * cin * cout * h * w * n):
-            _lib.call("ptmi_conv3x3_wgrad", _ptr(x), _ptr(dz), _ptr(dw), _ptr(db), _ptr(ws), n, cin, cout, h, w, 0, _stream())
+    ws_query, entry, key, issued, takes_waves = _WGRAD_ROUTES[_wgrad_kind(cin, cout, h, w)]
+    waves = (_WGRAD_WAVES,) if takes_waves else ()
+    ws = _ws("wgrad", getattr(_lib.load(), ws_query)(n, cin, cout, h, w, *waves) * 4, x.device)
+    with _prof(key, 2.0 * 9 * cin * cout * h * w * n, issued=issued(n, cin, cout, h, w) if issued else None):
+        _lib.call(entry, _ptr(x), _ptr(dz), _ptr(dw), _ptr(db), _ptr(ws), n, cin, cout, h, w, 0, *waves, _stream())
     return dw, db
 
 
 # ============================================================================ conv 3x3
-# Forward / dgrad algorithm of the fp32 3x3 layers: "auto" = fused Winograd F(4x4,3x3) (csrc/wino4.hip, round 5) where the
+# Forward / dgrad algorithm of the fp32 3x3 layers: "auto" = fused Winograd F(4x4,3x3) (csrc/wino4p.hip, round 6) where the
 # input channel count is a multiple of 8 and >= 64, else fused Winograd F(2x2,3x3) (csrc/wino.hip) wherever the
 # input has enough channels to amortise its per-workgroup prologue, the direct implicit GEMM (csrc/conv.hip) for the
 # 3-channel stem; "wino2" = as "auto" without the F(4x4,3x3) kernel; "direct" = the direct kernel everywhere (comparison
@@ -287,10 +275,11 @@ def wino_issued_flops(n: int, cin: int, cout: int, h: int, w: int) -> float:
 
 @functools.lru_cache(maxsize=256)
 def wino4_issued_flops(n: int, cin: int, cout: int, h: int, w: int) -> float:
-    """FLOPs of the v_mfma_f32_16x16x4_f32 instructions one ptmi_conv3x3_wino4_fwd launch issues: a wave runs 72 MFMAs
-    (2048 FLOP each: 36 positions x two 16-channel tiles) per 4-channel chunk for its 32 channels x 16 tiles (one tile row of
-    the FLAT tile line, csrc/wino4.hip); the persistent kernel runs every wave of every tile (a wave whose tile row lies below
-    the image would idle its SIMD either way).  (Checked against SQ_INSTS_VALU_MFMA_MOPS_F32 x 512, profiles/r05_*.)"""
+    """FLOPs of the v_mfma_f32_16x16x4_f32 instructions one ptmi_conv3x3_wino4{,p}_fwd launch issues: a wave runs 72 MFMAs
+    (2048 FLOP each) per 4-channel chunk for one tile row (16 tiles) of the FLAT tile line -- 36 positions x two 16-channel
+    tiles in csrc/wino4.hip, 18 positions x four in csrc/wino4p.hip (the default family); the persistent kernel runs every wave
+    of every tile (a wave whose tile row lies below the image would idle its SIMD either way).  (Checked against
+    SQ_INSTS_VALU_MFMA_MOPS_F32 x 512, profiles/r05_*.)"""
     co_tiles, chunks, bands = -(-cout // 64), cin // 4, -(-h // 8)
     period = (w + 4) & ~3
     n_pix = -(-(n * bands * period) // 64)
@@ -316,6 +305,17 @@ def wino_wgrad_issued_flops(n: int, cin: int, cout: int, h: int, w: int) -> floa
     return float(pairs) * chunks * ksn * 16 * 4 * 4096
 
 
+# _wgrad_kind -> (workspace query, entry point, profile key, issued-FLOP function, takes the `waves` argument): what
+# conv3x3_wgrad launches.  wino4w: csrc/wino4w.hip (workgroup = 64 co x 32 ci); wino: csrc/wino.hip; direct: csrc/conv.hip
+_WGRAD_ROUTES = {
+    "wino4w": ("ptmi_conv3x3_wino4_wgrad_ws_floats_waves", "ptmi_conv3x3_wino4_wgrad_waves", "conv3x3_wino4_wgrad",
+               wino4_wgrad_issued_flops, True),
+    "wino": ("ptmi_conv3x3_wino_wgrad_ws_floats_waves", "ptmi_conv3x3_wino_wgrad_waves", "conv3x3_wino_wgrad",
+             wino_wgrad_issued_flops, True),
+    "direct": ("ptmi_conv3x3_wgrad_ws_floats", "ptmi_conv3x3_wgrad", "conv3x3_wgrad", None, False),
+}
+
+
 def _use_wino(conv_cin: int, conv_cout: Optional[int] = None, hw: Optional[Tuple[int, int]] = None) -> bool:
     """Winograd routing of a 3x3 layer: fp32, enough input channels, and -- when the caller knows the map size -- a shape
     that fits the kernel's 32-bit buffer offsets (ptmi_conv3x3_wino_fwd_fits; larger maps run the direct kernel)."""
@@ -333,7 +333,7 @@ def _use_wino4(conv_cin: int, conv_cout: Optional[int] = None, hw: Optional[Tupl
         return False
     if hw is None or conv_cout is None:
         return True
-    return bool(getattr(_lib.load(), _CONV_ABI["wino4"] + "_fwd_fits")(conv_cin, conv_cout, int(hw[0]), int(hw[1])))
+    return bool(getattr(_lib.load(), _conv_abi("wino4") + "_fwd_fits")(conv_cin, conv_cout, int(hw[0]), int(hw[1])))
 
 
 def _conv_kind(conv_cin: int, conv_cout: Optional[int] = None, hw: Optional[Tuple[int, int]] = None) -> str:
@@ -348,12 +348,9 @@ def _conv_kind(conv_cin: int, conv_cout: Optional[int] = None, hw: Optional[Tupl
 _WINO4_FAMILY = "wino4p"
 
 
-class _ConvAbi(dict):
-    def __getitem__(self, kind):
-        return "ptmi_conv3x3_" + _WINO4_FAMILY if kind == "wino4" else dict.__getitem__(self, kind)
-
-
-_CONV_ABI = _ConvAbi({"wino4": "ptmi_conv3x3_wino4p", "wino": "ptmi_conv3x3_wino", "mfma": "ptmi_conv3x3"})
+def _conv_abi(kind: str) -> str:
+    """C-ABI prefix of a _conv_kind: the entry points are <prefix>_packed_floats / _pack_weights / _fwd (wino4: + _fwd_fits, _fwd_sched)"""
+    return {"wino4": "ptmi_conv3x3_" + _WINO4_FAMILY, "wino": "ptmi_conv3x3_wino", "mfma": "ptmi_conv3x3"}[kind]
 
 
 def set_wino4_family(name: str) -> None:
@@ -378,15 +375,16 @@ def conv3x3_pack(w: torch.Tensor, mode: int, epilogue: int, hw: Optional[Tuple[i
     _chk(w, name="conv weight")
     co, ci = w.shape[0], w.shape[1]
     conv_cin, conv_cout = (ci, co) if mode == 0 else (co, ci)
-    abi = _CONV_ABI[_conv_kind(conv_cin, conv_cout, hw)]
+    abi = _conv_abi(_conv_kind(conv_cin, conv_cout, hw))
     n = getattr(_lib.load(), abi + "_packed_floats")(conv_cin, conv_cout)
     wp = torch.empty(n, dtype=F32, device=w.device)
     _lib.call(abi + "_pack_weights", _ptr(w), _ptr(wp), co, ci, mode, _stream())
     return wp
 
 
-_TILE_SCHEDULE = "static"       # persistent F(4x4,3x3) kernel: "dynamic" (work queues, csrc/wino4.hip) | "static" (b, b + grid, ...);
-                                # PTrainer selects "dynamic" when the gradient exchange is active
+# Tile schedule of the persistent F(4x4,3x3) kernel (csrc/wino4p.hip; csrc/wino4.hip alike): "dynamic" (work queues) or "static"
+# (b, b + grid, ...).  PTrainer selects "dynamic" when the gradient exchange is active.
+_TILE_SCHEDULE = "static"
 _SCHED_BUFS: dict = {}
 
 
@@ -439,10 +437,10 @@ def _sched_buf(device):
 
 def _conv_fwd_call(kind: str, x, wp, bias, mask_ref, y, n, cin, cout, h, w, epilogue):
     if kind == "wino4":
-        _lib.call(_CONV_ABI[kind] + "_fwd_sched", _ptr(x), _ptr(wp), _ptr(bias), _ptr(mask_ref), _ptr(y), n, cin, cout, h, w,
+        _lib.call(_conv_abi(kind) + "_fwd_sched", _ptr(x), _ptr(wp), _ptr(bias), _ptr(mask_ref), _ptr(y), n, cin, cout, h, w,
                   epilogue, _ptr(_sched_buf(x.device)), _stream())
     else:
-        _lib.call(_CONV_ABI[kind] + "_fwd", _ptr(x), _ptr(wp), _ptr(bias), _ptr(mask_ref), _ptr(y), n, cin, cout, h, w, epilogue,
+        _lib.call(_conv_abi(kind) + "_fwd", _ptr(x), _ptr(wp), _ptr(bias), _ptr(mask_ref), _ptr(y), n, cin, cout, h, w, epilogue,
                   _stream())
 
 
@@ -454,7 +452,7 @@ def conv3x3_raw(x, wp, bias, mask_ref, cout: int, epilogue: int) -> torch.Tensor
     y = torch.empty((n, cout, h, w), dtype=F32, device=x.device)
     nbytes = 4.0 * (n * h * w * (cin + cout * (2 if epilogue == 3 else 1)) + 9 * cin * cout)
     kind = _conv_kind(cin, cout, (h, w))
-    abi = _CONV_ABI[kind]
+    abi = _conv_abi(kind)
     want = getattr(_lib.load(), abi + "_packed_floats")(cin, cout)
     if wp.numel() != want:
         raise _lib.PtmiError(f"conv3x3_raw: packed weights have {wp.numel()} floats, the {kind} kernel this {h}x{w} map is "

@@ -425,3 +425,33 @@ def test_eval_hooks_flatten_student_and_teacher_results():
     assert flat["bbox_student/AP"] == 10.0 and flat["bbox/AP"] == 20.0 and flat["bbox_student/AP50"] == 30.0
     assert flat["per_class_AP50_student/car"] == 1.0 and me._last_eval_results_teacher["bbox"]["AP"] == 20.0
 
+
+# (cin, cout, h, w) -> (packed floats, fits 32-bit buffer offsets), recorded from the build before the two families shared
+# their host side
+_WINO4_HOST_TABLE = {
+    (64, 64, 800, 1333): (147456, 1),
+    (128, 256, 200, 333): (1179648, 1),
+    (512, 512, 50, 83): (9437184, 1),
+    (512, 512, 1, 1): (9437184, 1),
+    (60, 64, 8, 8): (138240, 0),          # cin is no multiple of 8
+    (128, 128, 2000, 2050): (589824, 0),  # output side: (2 x 128 + 64) x 2000 x 2050 x 4 B = 5.2e9 >= 2^32
+}
+
+
+def test_wino4_families_share_packed_size_and_fits_predicate():
+    """Both F(4x4,3x3) forward families answer the host-side size / shape queries alike (one implementation behind both), as
+    the closed form says and as the library did before they shared it.  No device call."""
+    import ctypes
+    from probabilisticteacher_amd import build_ext
+    lib = ctypes.CDLL(build_ext.build())
+    for (cin, cout, h, w), (floats, fits) in _WINO4_HOST_TABLE.items():
+        got = []
+        for fam in ("wino4", "wino4p"):
+            packed = getattr(lib, f"ptmi_conv3x3_{fam}_packed_floats")
+            packed.restype, packed.argtypes = ctypes.c_int64, [ctypes.c_int] * 2
+            fwd_fits = getattr(lib, f"ptmi_conv3x3_{fam}_fwd_fits")
+            fwd_fits.restype, fwd_fits.argtypes = ctypes.c_int, [ctypes.c_int] * 4
+            got.append((packed(cin, cout), fwd_fits(cin, cout, h, w)))
+        assert got[0] == got[1], (cin, cout, h, w, got)
+        assert got[0][0] == -(-cout // 64) * -(-cin // 4) * 9216
+        assert got[0] == (floats, fits), (cin, cout, h, w, got)
