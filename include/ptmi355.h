@@ -523,6 +523,18 @@ int ptmi_get_deltas_bwd_src_det(const float* src, const float* tgt, const float*
                                 const int64_t* src_index, int64_t rows, float wx, float wy, float ww,
                                 float wh, float* dsrc, int64_t n_dst, float* ws, ptmi_stream_t s);
 
+/* ------------------------------------------------------------------ training statistics (integer counters)
+ * What the reference logs beside its losses.  Counts only: the ratios are formed on the host after the step's one
+ * metrics readback.  Two launches each (per-workgroup partial counts in ws, then their sum); no atomics, and integer
+ * sums do not depend on the order.  ws: 4096 int32.  counts_out is written in full; r == 0 / n == 0 writes zeros.
+ * D2 0.5 _log_classification_stats (FastRCNNOutputLayers.losses): logits (r, c) with c = K + 1, gt_classes (r) int64.
+ * counts_out[4] = rows with argmax == gt; rows with 0 <= gt < K (foreground); foreground rows with argmax == gt;
+ * foreground rows with argmax == K.  argmax = the lowest index among equal maxima; NaN logits: unspecified. */
+int ptmi_cls_stats(const float* logits, const int64_t* gt_classes, int64_t r, int c, int32_t* counts_out,
+                   int32_t* ws, ptmi_stream_t s);
+/* pt/modeling/proposal_generator/rpn.py:222-228: counts_out[2] = entries == 1, entries == 0 of the n int8 anchor labels. */
+int ptmi_label_counts(const int8_t* labels, int64_t n, int32_t* counts_out, int32_t* ws, ptmi_stream_t s);
+
 /* ------------------------------------------------------------------ optimiser / EMA (N15-N17)
  * flat fp32 buffers.  EMA: trainer.py:431-449  t = s*(1-k) + t*k  (that evaluation order). */
 int ptmi_ema_update(const float* student, float* teacher, int64_t n, float keep_rate,

@@ -123,6 +123,8 @@ SIGNATURES = {
     "ptmi_kl_efl_loss": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "ptmi_laplace_nll_sum": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _vp, _vp, _vp]),
     "ptmi_laplace_kl_efl_loss": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "ptmi_cls_stats": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "ptmi_label_counts": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "ptmi_get_deltas_bwd_src": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp, _vp]),
     "ptmi_get_deltas_bwd_src_det_ws_floats": (_i64, [_i64, _i64]),
     "ptmi_get_deltas_bwd_src_det": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp, _i64, _vp, _vp]),

@@ -13,6 +13,10 @@
 //   kl_efl_loss         rpn.py:321-355, fast_rcnn.py:215-263
 //   laplace_nll_sum     box_regression.py:38-40,177-183; fast_rcnn.py:298-307       (UNSUPNET.MODEL_TYPE = LAPLACE)
 //   laplace_kl_efl_loss rpn.py:319-344, fast_rcnn.py:238-257                         (UNSUPNET.MODEL_TYPE = LAPLACE)
+//
+// and the integer counters behind the logged training statistics (no loss, no gradient):
+//   cls_stats           D2 0.5 _log_classification_stats, reached from FastRCNNOutputLayers.losses
+//   label_counts        rpn.py:222-228
 #include "common.h"
 
 namespace {
@@ -376,6 +380,80 @@ __global__ __launch_bounds__(256) void lkl_efl_kernel(const float* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------ statistics (integer counts)
+// Sums of N int counters over a 256-thread block, stored by threads 0 .. N-1 to out[0 .. N-1].  smem: 4 N ints.
+// Integer addition: the result does not depend on the order, so neither does anything derived from it.
+template <int N>
+__device__ __forceinline__ void block_counts_store(const int (&c)[N], int* smem, int32_t* __restrict__ out)
+{
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        int v = c[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if ((threadIdx.x & 63) == 0) smem[(threadIdx.x >> 6) * N + k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < N)
+        out[threadIdx.x] = (smem[threadIdx.x] + smem[N + threadIdx.x]) + (smem[2 * N + threadIdx.x] + smem[3 * N + threadIdx.x]);
+}
+
+// ws[block][4] = (argmax == gt, gt foreground, foreground and argmax == gt, foreground and argmax == background) over the
+// block's rows.  One thread per row, as softmax_ce_kernel; the strict > keeps the lowest index among equal maxima.  gt is only
+// compared, never used as an index.
+__global__ __launch_bounds__(256) void cls_stats_kernel(const float* __restrict__ x, const int64_t* __restrict__ gt,
+                                                        int64_t R, int C, int32_t* __restrict__ ws)
+{
+    __shared__ int sm[16];
+    int c[4] = {0, 0, 0, 0};
+    const int K = C - 1;
+    for (int64_t r = blockIdx.x * 256ll + threadIdx.x; r < R; r += (int64_t)gridDim.x * 256) {
+        const float* p = x + r * C;
+        float m = p[0];
+        int am = 0;
+        for (int j = 1; j < C; ++j) {
+            const float v = p[j];
+            if (v > m) { m = v; am = j; }
+        }
+        const int64_t g = gt[r];
+        const bool fg = g >= 0 && g < K, hit = (int64_t)am == g;
+        c[0] += hit;
+        c[1] += fg;
+        c[2] += fg && hit;
+        c[3] += fg && am == K;
+    }
+    block_counts_store<4>(c, sm, ws + 4 * (int64_t)blockIdx.x);
+}
+
+// ws[block][2] = (labels == 1, labels == 0) over the block's share
+__global__ __launch_bounds__(256) void label_counts_kernel(const int8_t* __restrict__ lab, int64_t n,
+                                                           int32_t* __restrict__ ws)
+{
+    __shared__ int sm[8];
+    int c[2] = {0, 0};
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int l = lab[i];
+        c[0] += l == 1;
+        c[1] += l == 0;
+    }
+    block_counts_store<2>(c, sm, ws + 2 * (int64_t)blockIdx.x);
+}
+
+// out[0 .. N-1] = the sum of the nb block rows of ws; nb == 0 writes zeros
+template <int N>
+__global__ __launch_bounds__(256) void counts_final_kernel(const int32_t* __restrict__ ws, int nb, int32_t* __restrict__ out)
+{
+    __shared__ int sm[4 * N];
+    int c[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) c[k] = 0;
+    for (int i = threadIdx.x; i < nb; i += 256) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) c[k] += ws[N * i + k];
+    }
+    block_counts_store<N>(c, sm, out);
+}
+
 int finalize(float* ws, int nb, float scale, int mean_mode, float* loss_out, hipStream_t st, const char* name)
 {
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, st, ws, nb, scale, mean_mode, loss_out, ws + WS_SCALE);
@@ -541,6 +619,37 @@ int ptmi_laplace_kl_efl_loss(const float* q, const float* mu_p, const float* slo
             PTMI_LAUNCH_CHECK("lkl_scale_mu");
         }
     }
+    return 0;
+}
+
+int ptmi_cls_stats(const float* logits, const int64_t* gt_classes, int64_t r, int c, int32_t* counts_out, int32_t* ws,
+                   ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(counts_out && ws && r >= 0 && r <= 0x7fffffffll && c > 0, "cls_stats: bad args");
+    hipStream_t st = (hipStream_t)s;
+    const int nb = r > 0 ? blocks_for(r) : 0;
+    if (r > 0) {
+        PTMI_CHECK_ARG(logits && gt_classes, "cls_stats: null buffer");
+        hipLaunchKernelGGL(cls_stats_kernel, dim3(nb), dim3(256), 0, st, logits, gt_classes, r, c, ws);
+        PTMI_LAUNCH_CHECK("cls_stats");
+    }
+    hipLaunchKernelGGL(counts_final_kernel<4>, dim3(1), dim3(256), 0, st, ws, nb, counts_out);
+    PTMI_LAUNCH_CHECK("cls_stats_final");
+    return 0;
+}
+
+int ptmi_label_counts(const int8_t* labels, int64_t n, int32_t* counts_out, int32_t* ws, ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(counts_out && ws && n >= 0 && n <= 0x7fffffffll, "label_counts: bad args");
+    hipStream_t st = (hipStream_t)s;
+    const int nb = n > 0 ? blocks_for(n) : 0;
+    if (n > 0) {
+        PTMI_CHECK_ARG(labels, "label_counts: null buffer");
+        hipLaunchKernelGGL(label_counts_kernel, dim3(nb), dim3(256), 0, st, labels, n, ws);
+        PTMI_LAUNCH_CHECK("label_counts");
+    }
+    hipLaunchKernelGGL(counts_final_kernel<2>, dim3(1), dim3(256), 0, st, ws, nb, counts_out);
+    PTMI_LAUNCH_CHECK("label_counts_final");
     return 0;
 }
 

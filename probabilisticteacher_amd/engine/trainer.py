@@ -14,6 +14,7 @@ import torch.distributed as dist
 
 from .. import ops, seeding
 from ..modeling import EnsembleTSModel, build_model, sampling
+from ..modeling import statistics as step_statistics
 from ..structures import Boxes, FreeInstances
 from ..solver import check_optimizer_options, clip_gradients_options, lr_at
 from .flat import BucketedGradReducer, FlatParams, broadcast_, segment_offsets
@@ -26,12 +27,16 @@ class PTrainer:
         return 2 if amp else 3
 
     def __init__(self, cfg, data_loader=None, ratio_fn: Optional[Callable[[], float]] = None,
-                 force_grad_reducer: bool = False, grad_reduce: str = "all_reduce", deterministic: Optional[bool] = None):
+                 force_grad_reducer: bool = False, grad_reduce: str = "all_reduce", deterministic: Optional[bool] = None,
+                 statistics: bool = False):
         """force_grad_reducer: run the bucketed gradient all-reduce (hooks + collectives) even with one rank -- needs an
         initialised process group; the sum over one rank is the identity (single-GPU validation of the DDP path).
         grad_reduce: "all_reduce" or "reduce_scatter" (engine/flat.py: BucketedGradReducer).
         deterministic: run the step on the order-independent backward kernels (ops.deterministic), the static tile schedule and
-        one weight-gradient wave, so that same binary + same GPU model + same world size give the same bits; None = cfg.SEED >= 0."""
+        one weight-gradient wave, so that same binary + same GPU model + same world size give the same bits; None = cfg.SEED >= 0.
+        statistics: also log what the reference logs beside its losses -- `rpn/num_{pos,neg}_anchors`, `roi_head/num_target_{fg,bg}_
+        samples_<branch>`, `fast_rcnn/{cls_accuracy,fg_cls_accuracy,false_negative}` (modeling/statistics.py) -- into `last_metrics`:
+        two counting kernels in the supervised branch, no further device->host read.  Off: the step launches what it launched before."""
         self.cfg = cfg
         self.deterministic = cfg.SEED >= 0 if deterministic is None else bool(deterministic)
         check_optimizer_options(cfg)
@@ -44,6 +49,8 @@ class PTrainer:
         self.model_teacher = build_model(cfg)          # teacher (per-rank replica, never all-reduced)
         self.model.train()
         self.model_teacher.train()                     # the reference never puts the teacher in eval mode (:302-303)
+        # only the student computes losses, so only it counts (the reference's statistics all come from its supervised branch)
+        self._statistics = self.model.enable_statistics() if statistics else None
         for p in self.model_teacher.parameters():
             p.requires_grad_(False)
         self.student = FlatParams(self.model)
@@ -209,6 +216,8 @@ class PTrainer:
         data_time = time.perf_counter() - start
         U = self.cfg.UNSUPNET
         self.student.zero_grad()
+        if self._statistics is not None:
+            self._statistics.reset()
 
         if self.iter < U.BURN_UP_STEP:
             batch = self.resize(label_data_q + label_data_k)
@@ -250,6 +259,8 @@ class PTrainer:
         losses.backward()
         self.reducer.finish()                  # DDP gradient average (buckets were launched during backward)
         ss = self._clip_and_step(10.0)
+        if self._statistics is not None:
+            record_dict[step_statistics.KEY] = self._statistics
         self._write_metrics(record_dict, data_time, ss)
         self.iter += 1
         return self.last_metrics
@@ -263,7 +274,13 @@ class PTrainer:
         """trainer.py:394-429 with ONE device->host copy: all loss scalars packed into a single tensor (the
         reference does ~10 `.cpu().item()` syncs and a pickled gloo gather).  Multi-rank semantics of the reference:
         the keys of rank 0, each averaged over ALL ranks with 0.0 for a rank that lacks the key (:413-417); data_time is
-        the maximum over ranks (:407-411).  One all-gather of a fixed-layout vector (values + presence + data_time)."""
+        the maximum over ranks (:407-411).  One all-gather of a fixed-layout vector (values + presence + data_time).
+        A StatisticsSink under `record_dict["statistics"]` (PTrainer(statistics=True)) appends its device counts to that same
+        tensor.  They are rank-local, as the reference's event storage is rank 0's own: every rank reads its own row, as for
+        grad_norm; nothing is averaged.  The ratios are formed here, on the host, from the raw counts."""
+        stats = record_dict.get(step_statistics.KEY)
+        if stats is not None:
+            record_dict = {k: v for k, v in record_dict.items() if k != step_statistics.KEY}
         extra = [k for k in record_dict if k not in self.METRIC_KEYS]
         if self.world_size > 1 and extra:
             raise KeyError(f"metrics {extra} have no slot in the cross-rank layout (PTrainer.METRIC_KEYS)")
@@ -273,20 +290,23 @@ class PTrainer:
         present = [k in record_dict for k in keys]
         packed = torch.stack([record_dict[k].detach().float() if p else zero for k, p in zip(keys, present)] +
                              [sumsq.reshape(())])
+        tail = [stats.packed(dev)] if stats is not None else []
         if self.world_size > 1:
-            mine = torch.cat([packed, torch.tensor([float(p) for p in present] + [data_time], device=dev)])
+            mine = torch.cat([packed, torch.tensor([float(p) for p in present] + [data_time], device=dev)] + tail)
             allv = torch.empty(self.world_size * mine.numel(), device=dev)
             dist.all_gather_into_tensor(allv, mine)
             allv = allv.view(self.world_size, mine.numel()).cpu()
             nk = len(keys)
             mean = allv[:, :nk].mean(dim=0).tolist()            # absent entries were packed as 0.0
             m = {k: v for k, v, p in zip(keys, mean, allv[0, nk + 1:2 * nk + 1].tolist()) if p > 0}   # rank 0's keys
-            data_time = float(allv[:, -1].max())
+            data_time = float(allv[:, 2 * nk + 1].max())
             gsq = float(allv[dist.get_rank(), nk])
+            counts = allv[dist.get_rank(), 2 * nk + 2:].tolist()
         else:
-            vals = packed.cpu().tolist()
-            m = {k: v for k, v, p in zip(keys, vals[:-1], present) if p}
-            gsq = vals[-1]
+            vals = torch.cat([packed] + tail).cpu().tolist() if tail else packed.cpu().tolist()
+            m = {k: v for k, v, p in zip(keys, vals[:len(keys)], present) if p}
+            gsq = vals[len(keys)]
+            counts = vals[len(keys) + 1:]
         m["total_loss"] = sum(v for k, v in m.items() if k[:4] == "loss")
         # the fused ReLU (v_max_f32) turns a NaN pre-activation into 0 where torch.relu propagates it, so a diverged backbone
         # can hide from the loss values; the gradient norm (read back here anyway) is the cheap place where it still shows.
@@ -295,6 +315,8 @@ class PTrainer:
             raise FloatingPointError(f"non-finite gradient norm at iteration {self.iter} (losses {m})")
         m["grad_norm"] = gsq ** 0.5
         m["data_time"] = data_time
+        if stats is not None:
+            m.update(stats.metrics(counts))
         self.last_metrics = m
 
     # ------------------------------------------------------------------ evaluation (trainer.py:127-137, 529-542)

@@ -11,6 +11,7 @@ from ..structures import ImageList
 from .backbone import build_backbone
 from .roi_heads import build_roi_heads
 from .rpn import build_proposal_generator
+from .statistics import StatisticsSink
 
 
 @META_ARCH_REGISTRY.register()
@@ -25,6 +26,17 @@ class GuassianGeneralizedRCNN(nn.Module):
         self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(-1, 1, 1), False)
         self._mean = [float(v) for v in cfg.MODEL.PIXEL_MEAN]
         self._std = [float(v) for v in cfg.MODEL.PIXEL_STD]
+        self.statistics = None
+
+    def enable_statistics(self) -> StatisticsSink:
+        """Count what the reference logs beside its losses (modeling/statistics.py): ONE sink, owned here and handed to the
+        modules that count -- the RPN, the ROI head and its predictor.  Without this call their `statistics` stays None and they
+        launch nothing."""
+        self.statistics = StatisticsSink()
+        for m in (self.proposal_generator, self.roi_heads, getattr(self.roi_heads, "box_predictor", None)):
+            if m is not None:
+                m.statistics = self.statistics
+        return self.statistics
 
     @property
     def device(self):

@@ -153,6 +153,8 @@ class GuassianFastRCNNOutputLayers(nn.Module):
         self.test_topk_per_image = cfg.TEST.DETECTIONS_PER_IMAGE
         self.loss_weight = {"loss_cls": 1.0, "loss_box_reg": cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT}
 
+    statistics = None       # the meta-architecture's StatisticsSink (modeling/statistics.py); None = nothing is counted
+
     def forward(self, x):
         return (ops.linear(x, self.cls_score.weight, self.cls_score.bias, False),
                 ops.linear(x, self.bbox_pred.weight, self.bbox_pred.bias, False))
@@ -164,6 +166,8 @@ class GuassianFastRCNNOutputLayers(nn.Module):
         gt_classes = torch.cat([p.gt_classes for p in proposals], 0)
         pb = torch.cat([p.proposal_boxes.tensor for p in proposals], 0)
         gb = torch.cat([p.gt_boxes.tensor for p in proposals], 0)
+        if self.statistics is not None:                     # D2 0.5 _log_classification_stats, as device counts
+            self.statistics.put_classification(ops.cls_stats(scores, gt_classes), gt_classes.numel())
         loss_cls = ops.softmax_ce_mean(scores, gt_classes)
         fg = torch.nonzero((gt_classes >= 0) & (gt_classes < K)).squeeze(1)
         d = deltas.view(-1, K, 8)[fg, gt_classes[fg]]
@@ -291,6 +295,8 @@ class GuassianROIHead(nn.Module):
         self.box_predictor = GuassianFastRCNNOutputLayers(cfg, self.box_head.output_size)
         self.train_on_pred_boxes = B.TRAIN_ON_PRED_BOXES
 
+    statistics = None       # the meta-architecture's StatisticsSink (modeling/statistics.py); None = nothing is recorded
+
     def forward(self, images, features, proposals, targets=None, compute_loss=True, branch=""):
         if self.training and compute_loss:
             assert targets
@@ -351,6 +357,9 @@ class GuassianROIHead(nn.Module):
                         r.boxes_sigma = sel_sig[c0:c0 + cnt]
                 c0 += cnt
                 out.append(r)
+            if self.statistics is not None:                 # roi_heads.py:220-221: the reference appends zeros here
+                self.statistics.put_scalar("roi_head/num_target_fg_samples_" + branch, 0.0)
+                self.statistics.put_scalar("roi_head/num_target_bg_samples_" + branch, 0.0)
             return out
         # the whole batch at once.  Proposals (+ appended ground truth) of all images are
         # concatenated; labels come from one batched IoU match, the 512-per-image sample from one sampling launch
@@ -389,6 +398,9 @@ class GuassianROIHead(nn.Module):
         npos = int(self.batch_size_per_image * self.positive_fraction)
         fg, bg, cnt = ops.sample_by_keys(cls, keys, box_off, max(bcounts), self.batch_size_per_image, npos, K)
         cnt_h = cnt.cpu().tolist()                                                   # the one sync
+        if self.statistics is not None:                     # roi_heads.py:243-253: np.mean over the images, from that read
+            self.statistics.put_scalar("roi_head/num_target_fg_samples_" + branch, sum(nf for nf, _ in cnt_h) / len(cnt_h))
+            self.statistics.put_scalar("roi_head/num_target_bg_samples_" + branch, sum(nb for _, nb in cnt_h) / len(cnt_h))
         fg = fg + box_off[:-1].long().unsqueeze(1)
         bg = bg + box_off[:-1].long().unsqueeze(1)
         sel = torch.cat([t for i, (nf, nb) in enumerate(cnt_h) for t in (fg[i, :nf], bg[i, :nb])], 0)

@@ -131,6 +131,8 @@ class GuassianRPN(nn.Module):
         self.loss_weight = {"loss_rpn_cls": R.LOSS_WEIGHT, "loss_rpn_loc": R.BBOX_REG_LOSS_WEIGHT * R.LOSS_WEIGHT}
         self.nll_loss, self.kl_loss = uncertainty_losses(cfg.UNSUPNET.MODEL_TYPE)     # box_regression.py:177-183, rpn.py:319-344
 
+    statistics = None       # the meta-architecture's StatisticsSink (modeling/statistics.py); None = nothing is counted
+
     def head_outputs(self, feats):
         """the head's outputs in the flat anchor-order layout when the head offers it (no permute copies), else D2's"""
         flat = getattr(self.rpn_head, "forward_flat", None)
@@ -202,6 +204,8 @@ class GuassianRPN(nn.Module):
             midx, lab_all, _, gt_off, _ = ops.iou_match_batched(gt_all, counts, anc, None, self.iou_thresholds,
                                                                 self.iou_labels, True)
             lab_all = sampling.keyed_relabel(lab_all, self.batch_size_per_image, self.positive_fraction, 0)
+            if self.statistics is not None:                 # rpn.py:222-228, as device counts (no .item())
+                self.statistics.put_rpn_labels(ops.label_counts(lab_all), n, lab_all.numel())
             flat_pos = torch.nonzero(lab_all.view(-1) == 1).squeeze(1)
             img = torch.div(flat_pos, r, rounding_mode="floor")
             # (positives only exist for images with ground truth, so the gather index is always in range)

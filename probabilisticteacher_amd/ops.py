@@ -1335,6 +1335,30 @@ def softmax_rows(logits: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---------------------------------------------------------------------------- training statistics (integer counters)
+def cls_stats(logits: torch.Tensor, gt_classes: torch.Tensor) -> torch.Tensor:
+    """The counts behind fast_rcnn/cls_accuracy, fg_cls_accuracy and false_negative (D2 0.5 _log_classification_stats;
+    ptmi_cls_stats): logits (R, K + 1) fp32, gt_classes (R,) int64 -> int32 (4,) on the device = (argmax == gt, 0 <= gt < K,
+    foreground and argmax == gt, foreground and argmax == K).  Lowest index among equal maxima; R = 0 gives zeros.  No host read."""
+    logits = _chk(logits.detach().contiguous(), name="cls_stats logits")
+    gt_classes = _chk(gt_classes.contiguous(), torch.int64, "cls_stats gt_classes")
+    assert logits.dim() == 2 and gt_classes.shape == (logits.shape[0],)
+    out = torch.empty(4, dtype=torch.int32, device=logits.device)
+    _lib.call("ptmi_cls_stats", _ptr(logits), _ptr(gt_classes), logits.shape[0], logits.shape[1], _ptr(out),
+              _ptr(_ws("stats", 4096 * 4, logits.device)), _stream())
+    return out
+
+
+def label_counts(labels_i8: torch.Tensor) -> torch.Tensor:
+    """The counts behind rpn/num_pos_anchors and rpn/num_neg_anchors (rpn.py:222-228; ptmi_label_counts): int8 labels of any
+    shape -> int32 (2,) on the device = (entries == 1, entries == 0).  No host read."""
+    labels_i8 = _chk(labels_i8.contiguous(), torch.int8, "label_counts labels")
+    out = torch.empty(2, dtype=torch.int32, device=labels_i8.device)
+    _lib.call("ptmi_label_counts", _ptr(labels_i8), labels_i8.numel(), _ptr(out), _ptr(_ws("stats", 4096 * 4, labels_i8.device)),
+              _stream())
+    return out
+
+
 class _SoftCEEFL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, teacher, student, tau, lam, efl, inv_norm):

@@ -43,6 +43,8 @@ def main():
     ap.add_argument("--resume", action="store_true",
                     help="continue from MODEL.WEIGHTS (or OUTPUT_DIR/last_checkpoint): weights, optimiser state, iteration")
     ap.add_argument("--eval-only", action="store_true")
+    ap.add_argument("--no-statistics", action="store_true",
+                    help="log the losses only, without the rpn/ roi_head/ fast_rcnn/ statistics of a reference run's metrics.json")
     ap.add_argument("--register", action="append", default=[], metavar="NAME=DIR:SPLIT:CLS1,CLS2",
                     help="register a VOC-format directory as dataset NAME (Annotations/, JPEGImages/, ImageSets/Main/SPLIT.txt)")
     ap.add_argument("opts", nargs=argparse.REMAINDER)
@@ -69,7 +71,7 @@ def main():
         loader = synthetic_loader(cfg, torch.device("cuda", local), rank, world)
     else:
         loader = PTrainer.build_train_loader(cfg)              # trainer.py:139-141 -> pt/data/build.py:107
-    trainer = PTrainer(cfg, data_loader=loader)
+    trainer = PTrainer(cfg, data_loader=loader, statistics=not args.no_statistics)
     inc = trainer.resume_or_load(resume=args.resume)          # trainer.py:466-496 (no-op without MODEL.WEIGHTS / checkpoint)
     if inc is not None and rank == 0:
         print(f"loaded {cfg.MODEL.WEIGHTS or 'last_checkpoint'}: start_iter {trainer.start_iter}, "
