@@ -21,7 +21,8 @@
 //     fall on 16 distinct 16-byte bank groups.
 //   * three LDS stages of 40 KB (64 dY planes of 4 x 16 pixels, 32 x planes of 6 x 24), `buffer_load_dwordx4 ... lds`, ten DMA
 //     instructions per lane and chunk issued five per k-step, one and a half chunks ahead; ONE workgroup barrier per chunk behind
-//     a counted vmcnt(5); interior chunks use the lane's loop-invariant offsets, border chunks recompute per-piece validity.
+//     a counted vmcnt(5); interior chunks use the lane's loop-invariant offsets, border chunks mask them by per-lane validity
+//     bits built once; the descriptor bases advance by a step per chunk.
 //   * partial dU go to the workspace [split][position 36][co][ci]; the bias gradient (sum of dY) is accumulated by the row-(0,+a,-a)
 //     waves on every ciTiles-th chunk (each (co tile, ci tile) pair a different residue: together every chunk once) and appended
 //     as [split][ci tile][co]; wino4_wgrad_reduce sums splits in a fixed order (deterministic) and applies G^T . G.
@@ -157,83 +158,123 @@ __device__ __forceinline__ void wino4_wgrad_body(
     const int cBegin = split * per;
     const int nC = max(min(cBegin + per, nChunksAll) - cBegin, 0);
 
-    // ---- per-lane DMA pieces relative to the chunk's origin: dY (y0, x0), x (y0 - 1, x0 - 4); index 0 .. ZND-1 dY, then x
+    // ---- per-lane DMA pieces relative to the chunk's origin: dY (y0, x0), x (y0 - 1, x0 - 4); index 0 .. ZND-1 dY, then x.
+    // A piece is fetched iff (channel) & (column, by the class of the column block) & (row, by the class of the tile row).  All of it
+    // is loop-invariant per lane, so it is built ONCE, as bit masks over the lane's ten pieces (as wino.hip); a chunk on the image
+    // border combines them with wave-uniform selects.  The classes, each an independent flag:
+    //   first column block: the left halo pieces (x, column -4) are out;  last: pieces from column wl on;  top tile row: window row
+    //   y0 - 1;  bottom (= last) tile row: rows from hb on.  The x patch reaches column x0 + 19, so when the last block is narrower than
+    //   four columns the second-to-last block's right halo piece straddles the edge too: it stays valid and only gets fix-up bits.
+    const int wl = W - (colBlocks - 1) * 16;             // width of the last column block (1 .. 16)
+    const int hb = H - (tileRows - 1) * 4;               // rows of the last tile row (1 .. 4)
+    const int cbLast2 = wl < 4 ? colBlocks - 2 : -1;     // the column block before the last, where its halo straddles (-1: none such)
     unsigned voff[ZNP];
-    auto piece_coords = [&](int i, bool& chok, int& r, int& q4) __attribute__((always_inline)) {      // plane row / first column (relative) of piece i
+    unsigned inv_a = 0;                                  // pieces out in the first block (bits 0 .. 9) / the last (10 .. 19) / the top row (20 .. 29)
+    unsigned inv_b = 0;                                  // pieces out in the bottom row (bits 0 .. 9) / channel outside the tensor or pad (10 .. 19)
+    unsigned long long fix_last = 0, fix_last2 = 0;      // last / second-to-last column block: words past the image edge, bits 4 i + e
+#pragma unroll
+    for (int i = 0; i < ZNP; ++i) {
+        bool chok; int ch, r, q4, lev;                   // plane row / first column / row relative to y0 of piece i
         if (i < ZND) {
             const int pd = tid + i * ZNT;
-            const int ch = pd / ZDPC, rem = pd - ch * ZDPC;
-            r = rem >> 2; q4 = 4 * (rem & 3);
+            ch = pd / ZDPC;
+            const int rem = pd - ch * ZDPC;
+            r = rem >> 2; q4 = 4 * (rem & 3); lev = r;
             chok = pd < ZC * ZDPC && rem < 16 && co0 + ch < Cout;
         } else {
             const int px = tid + (i - ZND) * ZNT;
-            const int ch = px / ZXPC, rem = px - ch * ZXPC;
-            r = rem / 6; q4 = 4 * (rem - r * 6) - 4;
+            ch = px / ZXPC;
+            const int rem = px - ch * ZXPC;
+            r = rem / 6; q4 = 4 * (rem - r * 6) - 4; lev = r - 1;
             chok = px < ZI * ZXPC && rem < 36 && ci0 + ch < Cin;
         }
-    };
-#pragma unroll
-    for (int i = 0; i < ZNP; ++i) {
-        bool chok; int r, q4;
-        piece_coords(i, chok, r, q4);
-        const int ch = i < ZND ? (tid + i * ZNT) / ZDPC : (tid + (i - ZND) * ZNT) / ZXPC;
         voff[i] = chok ? (unsigned)(ch * HW + r * W + q4 + (i < ZND ? 0 : 4)) * 4u : 0xFFFFFFFFu;
+        inv_a |= (unsigned)(q4 < 0) << i | (unsigned)(q4 >= wl) << (10 + i) | (unsigned)(lev < 0) << (20 + i);
+        inv_b |= (unsigned)(lev >= hb) << i | (unsigned)!chok << (10 + i);
+        // (a piece whose row is masked needs no fix-up, and gets one all the same: zeroing zeros is harmless)
+        if (chok) {
+#pragma unroll
+            for (int e = 1; e < 4; ++e) {
+                fix_last |= (q4 < wl && q4 + e >= wl) ? (1ull << (4 * i + e)) : 0ull;
+                fix_last2 |= (q4 + e >= wl + 16) ? (1ull << (4 * i + e)) : 0ull;
+            }
+        }
     }
-    const char* x_end = (const char*)(x + (size_t)N * Cin * HW);
-    const char* dy_end = (const char*)(dy + (size_t)N * Cout * HW);
-    auto clamp_rec = [](long long rem) __attribute__((always_inline)) { return (int)(rem > 0xFFFFFFFEll ? 0xFFFFFFFEll : (rem < 0 ? 0 : rem)); };
+    // records of a descriptor: the bytes from its base to the tensor's end, clamped to [0, 2^32 - 2] -- a fetch never reaches past the
+    // tensor (on the 32-bit halves: 64-bit compares would go to the VALU)
+    auto clamp_rec = [](long long rem) __attribute__((always_inline)) {
+        const int hi = (int)(rem >> 32);
+        const unsigned lo = (unsigned)rem;
+        return (int)(hi < 0 ? 0u : ((hi > 0 || lo > 0xFFFFFFFEu) ? 0xFFFFFFFEu : lo));
+    };
 
     // ---- the fetch in progress: descriptors, effective per-piece offsets, fix-up masks (current and previous set-up)
-    int f_cb, f_ty, f_n;                                 // coordinates of the NEXT chunk to set up
+    int f_cb, f_ty;                                      // column block / tile row of the NEXT chunk to set up
+    // ... and its two patch origins as byte offsets from x / dy: x (y0 - 1, x0 - 4) of channel ci0, dY (y0, x0) of channel co0 (the
+    // first chunk's x origin lies before the tensor).  Advanced chunk by chunk -- 16 floats per column block, a row step and an image
+    // step at the wraps -- instead of rebuilt from the coordinates with 64-bit multiplies: every SALU instruction in the loop costs
+    // the lone wave of a SIMD issue time, as a VALU one does
+    long long xo, dO;
     {
         const int g = min(cBegin, max(nChunksAll - 1, 0));
         f_cb = g % colBlocks;
         const int t = g / colBlocks;
         f_ty = t % tileRows;
-        f_n = t / tileRows;
+        const int f_n = t / tileRows;
+        xo = (((long long)f_n * Cin + ci0) * HW + ((long long)4 * f_ty - 1) * W + (f_cb * 16 - 4)) * 4;
+        dO = (((long long)f_n * Cout + co0) * HW + (long long)4 * f_ty * W + f_cb * 16) * 4;
     }
     int f_left = nC;                                     // chunks of this split not yet set up
+    const long long x_bytes = (long long)N * Cin * HW * 4, dy_bytes = (long long)N * Cout * HW * 4;
+    const long long stepRow = ((long long)4 * W - 16 * (colBlocks - 1)) * 4;
+    const long long stepImgX = ((long long)Cin * HW - (long long)4 * (tileRows - 1) * W - 16 * (colBlocks - 1)) * 4;
+    const long long stepImgD = ((long long)Cout * HW - (long long)4 * (tileRows - 1) * W - 16 * (colBlocks - 1)) * 4;
     __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr(x), 0, 0, 0x00020000);
     __amdgpu_buffer_rsrc_t rd = rx;
-    unsigned eoff[ZNP];                                  // effective offsets of a chunk on the image border (else voff)
-    bool f_plain = false;
-    unsigned long long fix = 0, fix_prev = 0;            // words past the image edge, bits 4 i + e
+    // the offsets the DMA instructions use: ONE array, rewritten only when a chunk's class differs from the previous chunk's
+    // (interior after interior, or a run along one edge, rewrites nothing)
+    constexpr unsigned Z_FIRST = 2, Z_LAST = 4, Z_LAST2 = 8, Z_TOP = 16, Z_BOT = 32, Z_NONE = 64;   // (no flag is 1: a bool's zero-extension is selected on the VALU)
+    unsigned eoff[ZNP];
+#pragma unroll
+    for (int i = 0; i < ZNP; ++i) eoff[i] = voff[i];
+    unsigned e_cls = 0;                                  // the class eoff stands for (0: interior = voff)
+    unsigned long long fix = 0, fix_prev = 0;            // words past the image edge, bits 4 i + e (current and previous set-up)
     auto fetch_setup = [&]() __attribute__((always_inline)) {
-        const bool any = f_left > 0;
-        const int y0 = 4 * f_ty, x0 = f_cb * 16;
-        const float* xb = x + ((size_t)f_n * Cin + ci0) * HW + ((ptrdiff_t)y0 - 1) * W + (x0 - 4);
-        const float* db = dy + ((size_t)f_n * Cout + co0) * HW + (size_t)y0 * W + x0;
-        rx = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr(xb), 0, clamp_rec(x_end - (const char*)xb), 0x00020000);
-        rd = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr(db), 0, clamp_rec(dy_end - (const char*)db), 0x00020000);
+        rx = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr((const char*)x + xo), 0, clamp_rec(x_bytes - xo), 0x00020000);
+        rd = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr((const char*)dy + dO), 0, clamp_rec(dy_bytes - dO), 0x00020000);
         fix_prev = fix;
-        // interior chunk: every row and column of both patches inside the image -- the loop-invariant offsets serve
-        f_plain = any && x0 >= 4 && x0 + 20 <= W && y0 >= 1 && y0 + 5 <= H;
+        // class 0 = interior chunk: every row and column of both patches inside the image -- the loop-invariant offsets serve
+        const unsigned cls = f_left > 0 ? (f_cb == 0 ? Z_FIRST : 0u) | (f_cb == colBlocks - 1 ? Z_LAST : 0u) | (f_cb == cbLast2 ? Z_LAST2 : 0u) |
+                                              (f_ty == 0 ? Z_TOP : 0u) | (f_ty == tileRows - 1 ? Z_BOT : 0u)
+                                        : Z_NONE;
         fix = 0;
-        if (!f_plain) {
+        if (cls & (Z_LAST | Z_LAST2)) fix = (cls & Z_LAST) ? fix_last : fix_last2;
+        if (cls != e_cls) {
+            e_cls = cls;
+            if (cls == 0) {
 #pragma unroll
-            for (int i = 0; i < ZNP; ++i) {
-                bool chok; int r, q4;
-                piece_coords(i, chok, r, q4);
-                const int gy = y0 + r - (i < ZND ? 0 : 1), gx = x0 + q4;
-                const bool ok = any && chok && gy >= 0 && gy < H && gx >= 0 && gx < W;
-                eoff[i] = ok ? voff[i] : 0xFFFFFFFFu;
-                if (ok) {
+                for (int i = 0; i < ZNP; ++i) eoff[i] = voff[i];
+            } else {
+                const unsigned a = inv_a & ((cls & Z_FIRST ? 0x3FFu : 0u) | (cls & Z_LAST ? 0x3FFu << 10 : 0u) | (cls & Z_TOP ? 0x3FFu << 20 : 0u));
+                const unsigned b = inv_b & ((cls & Z_BOT ? 0x3FFu : 0u) | 0x3FFu << 10);
+                const unsigned inv = a | a >> 10 | a >> 20 | b | b >> 10 | (cls & Z_NONE ? 0x3FFu : 0u);
 #pragma unroll
-                    for (int e = 1; e < 4; ++e) fix |= (gx + e >= W) ? (1ull << (4 * i + e)) : 0ull;
-                }
+                for (int i = 0; i < ZNP; ++i) eoff[i] = voff[i] | (unsigned)((int)(inv << (31 - i)) >> 31);   // out: 0xFFFFFFFF
             }
         }
         --f_left;
+        long long sx = 64, sd = 64;
         if (++f_cb == colBlocks) {
             f_cb = 0;
-            if (++f_ty == tileRows) { f_ty = 0; ++f_n; }
+            sx = sd = stepRow;
+            if (++f_ty == tileRows) { f_ty = 0; sx = stepImgX; sd = stepImgD; }
         }
+        xo += sx;
+        dO += sd;
     };
     auto fetch_piece = [&](int idx, int stage) __attribute__((always_inline)) {
-        // (a scalar branch instead of a per-lane select: every VALU instruction in the loop costs MFMA time)
         zlds_void_t* dst = (zlds_void_t*)(lds + stage * ZSTAGE + (idx < ZND ? wave * 256 + idx * ZNT * 4 : ZDR + wave * 256 + (idx - ZND) * ZNT * 4));
-        if (f_plain) __builtin_amdgcn_raw_ptr_buffer_load_lds(idx < ZND ? rd : rx, dst, 16, (int)voff[idx], 0, 0, 0);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(idx < ZND ? rd : rx, dst, 16, (int)eoff[idx], 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(idx < ZND ? rd : rx, dst, 16, (int)eoff[idx], 0, 0, 0);
     };
     auto fixup = [&](int stage, unsigned long long fm) __attribute__((always_inline)) {
         if ((unsigned)fm | (unsigned)(fm >> 32)) {
