@@ -456,6 +456,33 @@ int ptmi_roi_infer_prepare(const float* deltas, const float* proposal_boxes, con
 int ptmi_roi_infer_nms_boxes(const float* boxes, const int32_t* order, const int32_t* seg_offsets,
                              const float* img_max, int nimg, int max_count, int k, float* out,
                              ptmi_stream_t s);
+/* NMS per (image, class) segment -- the path for many classes: the bitmask workspace of ptmi_nms_batched grows with
+ * nimg * k * max_r * ceil(max_r / 64) * 8 bytes here instead of nimg * (k max_r) * ceil(k max_r / 64) * 8.  The three entry
+ * points below feed ptmi_segsort_* / ptmi_nms_batched and collect from them; all share ONE description of the class-major
+ * layout: cls_seg_offsets (nimg * k + 1) int32, segment s = img * k + c holds the R_img entries of class c of image img in
+ * ROI order and starts at cls_seg_offsets[s] = k * roff[img] + c * R_img (roff = first ROI row of the image).  max_r = the
+ * largest R_img.  No host synchronisation; integer atomics only.
+ *
+ * class_keys: keys (R, k) of ptmi_roi_infer_prepare -> keys_out (k * R) class-major; seg_count_out (nimg * k) = number of
+ * candidates of the segment (key >= 0; every other entry holds -1). */
+int ptmi_roi_infer_class_keys(const float* keys, const int32_t* cls_seg_offsets, int nimg, int k, int max_r,
+                              float* keys_out, int32_t* seg_count_out, ptmi_stream_t s);
+/* class_nms_boxes: order = the index-within-segment output of a descending segmented sort of keys_out.  For segment
+ * (img, c), position p: out[beg + p] = boxes[roff[img] + order[beg + p]][c] + off in fp32, off = c * (img_max[img] + 1)
+ * while img_count[img] < 40000 (the bits ptmi_roi_infer_nms_boxes gives the same entry) and 0 otherwise: D2 0.5 batched_nms
+ * (fast_rcnn.py:104) leaves the coordinate-offset trick at 40 000 boxes for one NMS per class on the unshifted boxes. */
+int ptmi_roi_infer_class_nms_boxes(const float* boxes, const int32_t* order, const int32_t* cls_seg_offsets,
+                                   const float* img_max, const int32_t* img_count, int nimg, int k, int max_r,
+                                   float* out, ptmi_stream_t s);
+/* class_collect: keep (nimg * k, max_keep) / keep_count (nimg * k) of ptmi_nms_batched over the segments; sorted_keys /
+ * order of the segmented sort.  dense_keys_out (R, k), total = R * k entries: the key of every kept entry at its dense
+ * (roi, class) place, -1 everywhere else; img_kept_out (nimg) = kept entries of the image over all classes.  A stable
+ * descending sort of dense_keys_out per image lists the detections in batched_nms order (score descending, then ascending
+ * dense index roi * k + class). */
+int ptmi_roi_infer_class_collect(const float* sorted_keys, const int32_t* order, const int32_t* keep,
+                                 const int32_t* keep_count, const int32_t* cls_seg_offsets, int nimg, int k, int max_r,
+                                 int max_keep, int64_t total, float* dense_keys_out, int32_t* img_kept_out,
+                                 ptmi_stream_t s);
 
 /* ------------------------------------------------------------------ losses (N7, N8, N14)
  * Every loss kernel writes the scalar loss (already normalised) to loss_out[0] and the gradient

@@ -114,6 +114,9 @@ SIGNATURES = {
     "ptmi_nms_batched": (_i, [_vp, _vp, _vp, _i, _i64, _f, _i, _vp, _vp, _vp, _vp]),
     "ptmi_roi_infer_prepare": (_i, [_vp] * 11 + [_i64, _i, _i, _f, _f, _f, _f, _f, _f, _vp]),
     "ptmi_roi_infer_nms_boxes": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "ptmi_roi_infer_class_keys": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ptmi_roi_infer_class_nms_boxes": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "ptmi_roi_infer_class_collect": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp]),
     "ptmi_bce_logits_sum": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _vp, _vp]),
     "ptmi_gaussian_nll_sum": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _vp, _vp, _vp]),
     "ptmi_softmax_ce_mean": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp]),

@@ -645,6 +645,75 @@ __global__ void roi_infer_nms_boxes_kernel(const float* __restrict__ boxes, cons
     }
 }
 
+// ---------------------------------------------------------------------------------- ROI inference, NMS per (image, class)
+// The by-class path lays an image's dense (roi, class) entries out class-major: segment s = img * K + c holds the R_img entries
+// of class c in ROI order and starts at cseg[s] = K * roff[img] + c * R_img, so cseg (nimg * K + 1 offsets) describes the
+// whole layout: R_img = cseg[s + 1] - cseg[s], roff[img] = cseg[img * K] / K.  grid.x = segment, grid.y = 256-entry block.
+
+// dense keys (R, K) -> class-major keys + the number of candidates (key >= 0; every other entry holds -1) per segment
+__global__ __launch_bounds__(256) void roi_infer_class_keys_kernel(const float* __restrict__ keys,
+                                                                   const int32_t* __restrict__ cseg, int K,
+                                                                   float* __restrict__ out, int32_t* __restrict__ seg_cnt)
+{
+    const int s = blockIdx.x, img = s / K, c = s - img * K;
+    const int beg = cseg[s], n = cseg[s + 1] - beg;
+    const int64_t roff = cseg[img * K] / K;
+    const int p = blockIdx.y * 256 + threadIdx.x;
+    bool cand = false;
+    if (p < n) {
+        const float key = keys[(roff + p) * K + c];
+        out[beg + p] = key;
+        cand = key >= 0.f;
+    }
+    const unsigned long long m = __ballot(cand);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(seg_cnt + s, __popcll(m));
+}
+
+// boxes handed to NMS, per (image, class) segment in sorted order: box + off in fp32 with off = c * (img_max + 1) while the
+// image has fewer than 40 000 candidates (the expression of roi_infer_nms_boxes_kernel, bit for bit) and 0 from there on:
+// D2 0.5 batched_nms runs one NMS per class on the unshifted boxes at >= 40 000
+__global__ __launch_bounds__(256) void roi_infer_class_nms_boxes_kernel(const float* __restrict__ boxes,
+                                                                        const int32_t* __restrict__ order,
+                                                                        const int32_t* __restrict__ cseg,
+                                                                        const unsigned* __restrict__ img_max,
+                                                                        const int32_t* __restrict__ img_cnt, int K,
+                                                                        float* __restrict__ out)
+{
+    const int s = blockIdx.x, img = s / K, c = s - img * K;
+    const int beg = cseg[s], n = cseg[s + 1] - beg;
+    const int p = blockIdx.y * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int64_t roff = cseg[img * K] / K;
+    const float off1 = __uint_as_float(img_max[img]) + 1.0f;
+    const float off = img_cnt[img] < 40000 ? (float)c * off1 : 0.f;
+    const int o = order[beg + p];
+    if (o < 0 || o >= n) return;                       // (never: the sort emits positions inside the segment)
+    const float4 b = reinterpret_cast<const float4*>(boxes)[(roff + o) * K + c];
+    reinterpret_cast<float4*>(out)[beg + p] = make_float4(b.x + off, b.y + off, b.z + off, b.w + off);
+}
+
+// kept entries of every segment back to the dense (R, K) key array (pre-filled with -1) + kept entries per image
+__global__ __launch_bounds__(256) void roi_infer_class_collect_kernel(const float* __restrict__ sorted_keys,
+                                                                      const int32_t* __restrict__ order,
+                                                                      const int32_t* __restrict__ keep,
+                                                                      const int32_t* __restrict__ keep_cnt,
+                                                                      const int32_t* __restrict__ cseg, int K, int max_keep,
+                                                                      float* __restrict__ dense, int32_t* __restrict__ img_kept)
+{
+    const int s = blockIdx.x, img = s / K, c = s - img * K;
+    const int beg = cseg[s], n = cseg[s + 1] - beg;
+    const int kc = min(min(keep_cnt[s], max_keep), n);
+    const int j = blockIdx.y * 256 + threadIdx.x;
+    if (j == 0 && kc > 0) atomicAdd(img_kept + img, kc);
+    if (j >= kc) return;
+    const int p = keep[(int64_t)s * max_keep + j];
+    if (p < 0 || p >= n) return;                       // (never: NMS emits positions inside the segment)
+    const int o = order[beg + p];
+    if (o < 0 || o >= n) return;
+    const int64_t roff = cseg[img * K] / K;
+    dense[(roff + o) * K + c] = sorted_keys[beg + p];
+}
+
 inline unsigned grid_for(int64_t n)
 {
     int64_t b = (n + 255) / 256;
@@ -874,6 +943,67 @@ int ptmi_roi_infer_nms_boxes(const float* boxes, const int32_t* order, const int
     hipLaunchKernelGGL(roi_infer_nms_boxes_kernel, dim3(cdiv(max_count, 256), nimg), dim3(256), 0, (hipStream_t)s, boxes,
                        order, seg_offsets, reinterpret_cast<const unsigned*>(img_max), k, out);
     PTMI_LAUNCH_CHECK("roi_infer_nms_boxes");
+    return 0;
+}
+
+// shared argument checks of the by-class entry points: grid = (nimg * k segments, 256-entry blocks of the longest one); at most
+// 65 535 segments, the grid.z range ptmi_nms_batched spreads them over
+#define PTMI_CLASS_SEG_ARGS(name)                                                                                         \
+    PTMI_CHECK_ARG(cls_seg_offsets && nimg > 0 && k > 0 && (int64_t)nimg * k <= 65535 && max_r >= 0 &&                   \
+                       max_r <= 65535 * 256,                                                                              \
+                   name ": bad args")
+
+int ptmi_roi_infer_class_keys(const float* keys, const int32_t* cls_seg_offsets, int nimg, int k, int max_r,
+                              float* keys_out, int32_t* seg_count_out, ptmi_stream_t s)
+{
+    PTMI_CLASS_SEG_ARGS("roi_infer_class_keys");
+    PTMI_CHECK_ARG(seg_count_out, "roi_infer_class_keys: null buffer");
+    hipStream_t st = (hipStream_t)s;
+    if (hipMemsetAsync(seg_count_out, 0, sizeof(int32_t) * (size_t)nimg * k, st) != hipSuccess) {
+        ptmi_set_error("roi_infer_class_keys: memset failed");
+        return -2;
+    }
+    if (max_r == 0) return 0;
+    PTMI_CHECK_ARG(keys && keys_out, "roi_infer_class_keys: null buffer");
+    hipLaunchKernelGGL(roi_infer_class_keys_kernel, dim3(nimg * k, cdiv(max_r, 256)), dim3(256), 0, st, keys, cls_seg_offsets,
+                       k, keys_out, seg_count_out);
+    PTMI_LAUNCH_CHECK("roi_infer_class_keys");
+    return 0;
+}
+
+int ptmi_roi_infer_class_nms_boxes(const float* boxes, const int32_t* order, const int32_t* cls_seg_offsets,
+                                   const float* img_max, const int32_t* img_count, int nimg, int k, int max_r, float* out,
+                                   ptmi_stream_t s)
+{
+    PTMI_CLASS_SEG_ARGS("roi_infer_class_nms_boxes");
+    PTMI_CHECK_ARG(img_max && img_count, "roi_infer_class_nms_boxes: null buffer");
+    if (max_r == 0) return 0;
+    PTMI_CHECK_ARG(boxes && order && out, "roi_infer_class_nms_boxes: null buffer");
+    hipLaunchKernelGGL(roi_infer_class_nms_boxes_kernel, dim3(nimg * k, cdiv(max_r, 256)), dim3(256), 0, (hipStream_t)s, boxes,
+                       order, cls_seg_offsets, reinterpret_cast<const unsigned*>(img_max), img_count, k, out);
+    PTMI_LAUNCH_CHECK("roi_infer_class_nms_boxes");
+    return 0;
+}
+
+int ptmi_roi_infer_class_collect(const float* sorted_keys, const int32_t* order, const int32_t* keep,
+                                 const int32_t* keep_count, const int32_t* cls_seg_offsets, int nimg, int k, int max_r,
+                                 int max_keep, int64_t total, float* dense_keys_out, int32_t* img_kept_out, ptmi_stream_t s)
+{
+    PTMI_CLASS_SEG_ARGS("roi_infer_class_collect");
+    PTMI_CHECK_ARG(img_kept_out && max_keep > 0 && total >= 0 && total < (1ll << 31), "roi_infer_class_collect: bad args");
+    hipStream_t st = (hipStream_t)s;
+    hipError_t e = hipMemsetAsync(img_kept_out, 0, sizeof(int32_t) * (size_t)nimg, st);
+    if (e == hipSuccess && total > 0) {
+        PTMI_CHECK_ARG(dense_keys_out, "roi_infer_class_collect: null buffer");
+        e = hipMemsetD32Async((hipDeviceptr_t)dense_keys_out, (int)0xBF800000u, (size_t)total, st);      // -1.0f
+    }
+    if (e != hipSuccess) { ptmi_set_error("roi_infer_class_collect: memset failed"); return -2; }
+    if (max_r == 0 || total == 0) return 0;
+    PTMI_CHECK_ARG(sorted_keys && order && keep && keep_count, "roi_infer_class_collect: null buffer");
+    const int blocks = cdiv(max_keep < max_r ? max_keep : max_r, 256);
+    hipLaunchKernelGGL(roi_infer_class_collect_kernel, dim3(nimg * k, blocks), dim3(256), 0, st, sorted_keys, order, keep,
+                       keep_count, cls_seg_offsets, k, max_keep, dense_keys_out, img_kept_out);
+    PTMI_LAUNCH_CHECK("roi_infer_class_collect");
     return 0;
 }
 

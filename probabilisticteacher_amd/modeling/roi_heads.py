@@ -132,6 +132,41 @@ def build_box_head(cfg, input_shape):
     return ROI_BOX_HEAD_REGISTRY.get(cfg.MODEL.ROI_BOX_HEAD.NAME)(cfg, input_shape)
 
 
+# ---- teacher inference: one NMS per image over all (roi, class) entries, or one per (image, class)
+NMS_DENSE_AUTO_MAX = 16384      # entries per image the LDS segmented sort holds: the dense path's range when left on auto
+NMS_SEGMENT_MAX = 524288        # boxes per NMS segment: the scan kernel keeps one row of the bitmask in LDS (64 KB)
+
+
+def nms_ws_bytes_dense(nimg: int, num_classes: int, max_r: int) -> int:
+    """bitmask workspace of the dense path: one segment of K * max R_i entries per image"""
+    cap = num_classes * max_r
+    return nimg * cap * ((cap + 63) // 64) * 8
+
+
+def nms_ws_bytes_by_class(nimg: int, num_classes: int, max_r: int) -> int:
+    """bitmask workspace of the by-class path: K segments of max R_i entries per image"""
+    return nimg * num_classes * max_r * ((max_r + 63) // 64) * 8
+
+
+def select_nms_by_class(num_classes: int, counts, nms_by_class: Optional[bool] = None) -> bool:
+    """Which path `GuassianFastRCNNOutputLayers.inference` takes for a batch with counts[i] proposals in image i: True = NMS per
+    (image, class) segment, False = one NMS per image over its dense K * R_i (roi, class) entries.  None decides by size: dense
+    while K * max R_i <= 16 384 (every shipped config: K = 8 x 2000 proposals, K = 1), by class above; True / False force a
+    path.  Raises ValueError for a segment the single-pass bitmask NMS cannot hold (524 288 boxes): K * max R_i on the dense
+    path, max R_i on the by-class path."""
+    max_r = max(counts) if len(counts) else 0
+    cap = num_classes * max_r
+    by_class = cap > NMS_DENSE_AUTO_MAX if nms_by_class is None else bool(nms_by_class)
+    if not by_class and cap > NMS_SEGMENT_MAX:
+        raise ValueError(f"ROI inference: {num_classes} classes x {max_r} proposals = {cap} NMS candidates per image exceed the "
+                         f"{NMS_SEGMENT_MAX} the single-pass bitmask NMS holds; leave nms_by_class on None / True or lower "
+                         "MODEL.RPN.POST_NMS_TOPK_TEST")
+    if by_class and max_r > NMS_SEGMENT_MAX:
+        raise ValueError(f"ROI inference: {max_r} proposals per image exceed the {NMS_SEGMENT_MAX} the single-pass bitmask NMS "
+                         "holds per class; lower MODEL.RPN.POST_NMS_TOPK_TEST")
+    return by_class
+
+
 class GuassianFastRCNNOutputLayers(nn.Module):
     """cls_score (K+1) and bbox_pred (8K) + Gaussian / entropy-focal losses + teacher inference
     (fast_rcnn.py:145-409)."""
@@ -154,6 +189,7 @@ class GuassianFastRCNNOutputLayers(nn.Module):
         self.loss_weight = {"loss_cls": 1.0, "loss_box_reg": cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT}
 
     statistics = None       # the meta-architecture's StatisticsSink (modeling/statistics.py); None = nothing is counted
+    nms_by_class: Optional[bool] = None     # inference(): None = by size (select_nms_by_class), True / False force a path
 
     def forward(self, x):
         return (ops.linear(x, self.cls_score.weight, self.cls_score.bias, False),
@@ -205,7 +241,9 @@ class GuassianFastRCNNOutputLayers(nn.Module):
         per-image candidate count / max coordinate) in one launch and leaves dense (roi, class) arrays; candidates are
         never compacted on the host: a segmented stable sort of the keys over the fixed (R_i * K)-entry segments puts
         each image's candidates first, in the order batched_nms visits them, and the NMS runs on the first count[i]
-        entries (counts stay on the device).  ONE device->host read per call (the kept-detection counts)."""
+        entries (counts stay on the device).  With many classes (select_nms_by_class) the same entries go through NMS as one
+        segment per (image, class) instead, and the kept ones are merged per image.  ONE device->host read per call (the
+        kept-detection counts) on either path."""
         scores, deltas = predictions
         K = self.num_classes
         dev = scores.device
@@ -225,23 +263,48 @@ class GuassianFastRCNNOutputLayers(nn.Module):
             deltas.contiguous(), pb, probs, roi_img, hw, K, self.box2box_transform.weights,
             self.box2box_transform.scale_clamp, self.test_score_thresh)
         seg = ops.dev_i32([K * o for o in roff], dev)                     # dense (roi, class) segments per image
-        # NMS capacity = the dense segment length K * max R_i (no host read to learn the candidate count).  Memory law of the
-        # bitmask workspace: images * cap * ceil(cap / 64) * 8 bytes -- 32 MB per image at K = 8, R = 2000 (the shipped
-        # configs, ~0.5 GB for 16 images), ~200 MB per image at K = 20, ~3.2 GB per image at K = 80; the scan kernel keeps one
-        # row of the mask in LDS, which caps cap at 524 288 candidates per image.
-        cap = K * max(counts) if counts else 0
-        if cap > 524288:
-            raise ValueError(f"ROI inference: {K} classes x {max(counts)} proposals = {cap} NMS candidates per image exceed the "
-                             "524 288 the single-pass bitmask NMS holds; lower MODEL.RPN.POST_NMS_TOPK_TEST")
-        srt, order = ops.segsort_desc(keys.view(-1), seg, max_len=cap, lengths=[K * c for c in counts])
-        nms_boxes = ops.roi_infer_nms_boxes(boxes, order, seg, img_max, cap, K)
-        topk = self.test_topk_per_image if self.test_topk_per_image >= 0 else max(cap, 1)
-        keep, kcnt = ops.nms_batched(nms_boxes, seg, cap, float(self.test_nms_thresh), int(max(topk, 1)),
-                                     seg_counts=img_cnt)
-        host = torch.cat([kcnt, img_inv]).cpu().tolist()                  # the one sync
-        kc, dropped = host[:n], host[n:]
-        keep_g = keep.long() + seg[:-1].long().unsqueeze(1)                # (seg[i] = K * roff[i])
-        pos = torch.cat([keep_g[i, :kc[i]] for i in range(n)], 0) if n else seg[:0].long()
+        # NMS capacity = the segment length (no host read to learn the candidate count), and the bitmask workspace is
+        # segments * capacity * ceil(capacity / 64) * 8 bytes.  Two layouts, chosen by select_nms_by_class:
+        #   dense     one segment of K * max R_i entries per image: 32 MB per image at K = 8, R = 2000 (the shipped configs,
+        #             ~0.5 GB for 16 images), but 200 MB per image at K = 20 and 3.2 GB at K = 80 -- it grows with (K R)^2;
+        #   by class  K segments of max R_i entries per image: 4 MB per (image, 8 classes) at R = 2000 -- 65 / 164 / 655 MB
+        #             for 16 images at K = 8 / 20 / 80.  Pairs of different classes never suppress each other, so only this
+        #             much of the dense mask was ever needed.
+        # The scan kernel keeps one row of the mask in LDS, which caps a segment at 524 288 boxes.
+        max_r = max(counts) if counts else 0
+        cap = K * max_r
+        lengths = [K * c for c in counts]
+        det_max = self.test_topk_per_image
+        if select_nms_by_class(K, counts, self.nms_by_class):
+            # class-major keys, one sort + one NMS over the n * K (image, class) segments, kept entries back to the dense
+            # array; its stable descending sort per image is batched_nms's order (score, then dense index roi * K + class)
+            cseg_h = ops.roi_class_seg_offsets(counts, K)
+            cseg = ops.dev_i32(cseg_h, dev)
+            ckeys, ccnt = ops.roi_infer_class_keys(keys, cseg, n, K, max_r)
+            csrt, corder = ops.segsort_desc(ckeys, cseg, max_len=max_r, lengths=[c for c in counts for _ in range(K)])
+            nms_boxes = ops.roi_infer_class_nms_boxes(boxes, corder, cseg, img_max, img_cnt, n, K, max_r)
+            # (no class contributes more than DETECTIONS_PER_IMAGE entries to the image's top-k)
+            keep_c = max(min(max_r, det_max) if det_max >= 0 else max_r, 1)
+            keep, kcnt = ops.nms_batched(nms_boxes, cseg, max_r, float(self.test_nms_thresh), int(keep_c), seg_counts=ccnt)
+            kept_keys, img_kept = ops.roi_infer_class_collect(csrt, corder, keep, kcnt, cseg, n, K, max_r, R)
+            srt, order = ops.segsort_desc(kept_keys.view(-1), seg, max_len=cap, topk=det_max if det_max > 0 else None,
+                                          lengths=lengths)
+            host = torch.cat([img_kept, img_inv]).cpu().tolist()          # the one sync
+            kc, dropped = host[:n], host[n:]
+            if det_max >= 0:
+                kc = [min(k, det_max) for k in kc]
+            first = seg[:-1].long()
+            pos = torch.cat([first[i] + torch.arange(kc[i], device=dev) for i in range(n)], 0) if n else seg[:0].long()
+        else:
+            srt, order = ops.segsort_desc(keys.view(-1), seg, max_len=cap, lengths=lengths)
+            nms_boxes = ops.roi_infer_nms_boxes(boxes, order, seg, img_max, cap, K)
+            topk = det_max if det_max >= 0 else max(cap, 1)
+            keep, kcnt = ops.nms_batched(nms_boxes, seg, cap, float(self.test_nms_thresh), int(max(topk, 1)),
+                                         seg_counts=img_cnt)
+            host = torch.cat([kcnt, img_inv]).cpu().tolist()              # the one sync
+            kc, dropped = host[:n], host[n:]
+            keep_g = keep.long() + seg[:-1].long().unsqueeze(1)            # (seg[i] = K * roff[i])
+            pos = torch.cat([keep_g[i, :kc[i]] for i in range(n)], 0) if n else seg[:0].long()
         img_base = torch.repeat_interleave(seg[:-1].long(), ops.dev_i32(kc, dev).long(), output_size=sum(kc))
         dense = img_base + order[pos].long()                              # flat (roi, class) index of every detection
         roi, cls = torch.div(dense, K, rounding_mode="floor"), dense % K

@@ -1241,6 +1241,47 @@ def roi_infer_nms_boxes(boxes, order, seg_offsets, img_max, max_count: int, k: i
     return out
 
 
+def roi_class_seg_offsets(counts: Sequence[int], k: int) -> list:
+    """Host list of the nimg * k + 1 offsets of the class-major layout of ROI inference by class (include/ptmi355.h): segment
+    img * k + c = the counts[img] entries of class c of image img, starting at k * roff[img] + c * counts[img]."""
+    offs, base = [], 0
+    for c in counts:
+        offs.extend(base + j * int(c) for j in range(k))
+        base += k * int(c)
+    offs.append(base)
+    return offs
+
+
+def roi_infer_class_keys(keys, cls_seg, nimg: int, k: int, max_r: int):
+    """dense keys (R, K) -> class-major keys (K * R,) and the candidate count of every (image, class) segment, int32."""
+    out = torch.empty(keys.numel(), dtype=F32, device=keys.device)
+    cnt = torch.empty(nimg * k, dtype=torch.int32, device=keys.device)
+    _lib.call("ptmi_roi_infer_class_keys", _ptr(_chk(keys)), _ptr(_chk(cls_seg, torch.int32)), nimg, k, int(max_r), _ptr(out),
+              _ptr(cnt), _stream())
+    return out, cnt
+
+
+def roi_infer_class_nms_boxes(boxes, order, cls_seg, img_max, img_count, nimg: int, k: int, max_r: int) -> torch.Tensor:
+    """the boxes NMS sees, per (image, class) segment in sorted order (class offset below 40 000 candidates per image)"""
+    out = torch.empty((boxes.shape[0] * boxes.shape[1], 4), dtype=F32, device=boxes.device)
+    _lib.call("ptmi_roi_infer_class_nms_boxes", _ptr(_chk(boxes)), _ptr(_chk(order, torch.int32)),
+              _ptr(_chk(cls_seg, torch.int32)), _ptr(_chk(img_max)), _ptr(_chk(img_count, torch.int32)), nimg, k, int(max_r),
+              _ptr(out), _stream())
+    return out
+
+
+def roi_infer_class_collect(sorted_keys, order, keep, keep_count, cls_seg, nimg: int, k: int, max_r: int, rows: int):
+    """kept entries of every (image, class) segment -> dense keys (rows, K) (-1 where nothing was kept) and the kept count per
+    image, int32"""
+    dense = torch.empty((rows, k), dtype=F32, device=sorted_keys.device)
+    kept = torch.empty(nimg, dtype=torch.int32, device=sorted_keys.device)
+    assert keep.dim() == 2 and keep.shape[0] == nimg * k and keep_count.numel() == nimg * k
+    _lib.call("ptmi_roi_infer_class_collect", _ptr(_chk(sorted_keys)), _ptr(_chk(order, torch.int32)),
+              _ptr(_chk(keep, torch.int32)), _ptr(_chk(keep_count, torch.int32)), _ptr(_chk(cls_seg, torch.int32)), nimg, k,
+              int(max_r), keep.shape[1], rows * k, _ptr(dense), _ptr(kept), _stream())
+    return dense, kept
+
+
 # ============================================================================ losses (loss + gradient in one launch)
 class _BCELogitsSum(torch.autograd.Function):
     @staticmethod
