@@ -484,6 +484,28 @@ int ptmi_roi_infer_class_collect(const float* sorted_keys, const int32_t* order,
                                  int max_keep, int64_t total, float* dense_keys_out, int32_t* img_kept_out,
                                  ptmi_stream_t s);
 
+/* ------------------------------------------------------------------ COCO evaluation: detection <-> ground-truth matching
+ * pycocotools COCOeval.computeIoU / evaluateImg with maskApi.c bbIou (detectron2 COCOEvaluator, pt/engine/trainer.py:132-133)
+ * for ALL nseg (image, category) segments of an evaluation in one launch.  Segment i holds detections
+ * [dt_off[i], dt_off[i+1]) of dt_xywh (nd,4) / dt_area (nd), already in descending-score order, and ground truth
+ * [gt_off[i], gt_off[i+1]) of gt_xywh (ng,4) / gt_area (ng) / gt_crowd (ng) int32 in dataset order; both tables int64[nseg+1],
+ * ascending, tiling [0, nd) and [0, ng).  iou_thr (nthr <= 16), area_rng (narea <= 4, 2) [lo, hi].  All float64.
+ * Outputs (written in full when the tables tile the arrays): gt_ignore (narea, ng) = crowd || area < lo || area > hi;
+ * dt_match (narea, nthr, nd) = position of the matched GT inside its segment or -1; dt_ignore (narea, nthr, nd) = the matched
+ * GT's ignore flag, or for an unmatched detection "its own area lies outside [lo, hi]".
+ * IoU = i / (crowd ? da : da + ga - i), i = w h of the overlap (0 when w <= 0 or h <= 0), no + 1, in double and in that
+ * operation order.  Per (range, threshold), detections in order: best = min(thr, 1 - 1e-10); GT visited non-ignored first, then
+ * ignored, each in dataset order; a GT already matched is skipped unless crowd; the scan ends when it holds a non-ignored match
+ * and reaches the ignored GT; a GT with iou < best is skipped, every other one becomes the match and raises best to its iou.
+ * max_dt / max_gt = the longest segment of either table, known to the caller: max_dt > 100 (maxDets[-1]),
+ * max_gt > ptmi_coco_match_max_gt() (1024), nthr > 16 or narea > 4 is an error BEFORE anything is launched; a segment longer than
+ * announced is left untouched by the kernel.  One wave per segment, a lane per (range, threshold); no atomics. */
+int ptmi_coco_match_max_gt(void);
+int ptmi_coco_match(const double* dt_xywh, const double* dt_area, const int64_t* dt_off, const double* gt_xywh,
+                    const double* gt_area, const int32_t* gt_crowd, const int64_t* gt_off, int64_t nseg, int64_t nd,
+                    int64_t ng, int max_dt, int max_gt, const double* iou_thr, int nthr, const double* area_rng, int narea,
+                    int32_t* gt_ignore, int32_t* dt_match, int32_t* dt_ignore, ptmi_stream_t s);
+
 /* ------------------------------------------------------------------ losses (N7, N8, N14)
  * Every loss kernel writes the scalar loss (already normalised) to loss_out[0] and the gradient
  * w.r.t. its differentiable inputs (already multiplied by 1/normaliser) in the same launch;

@@ -126,6 +126,9 @@ def _test_record(cfg, d: dict, m: dict, dev) -> dict:
     if "boxes" in m:
         inst = FreeInstances((h, w))
         inst.gt_boxes, inst.gt_classes, inst.difficult = Boxes(m["boxes"]), m["classes"], m["difficult"]
+        for k in ("iscrowd", "area"):                 # COCO-format datasets only (the COCO evaluator's dict-less path)
+            if k in m:
+                inst.set(k, m[k])
         rec["instances"] = inst
     return rec
 
@@ -145,7 +148,7 @@ def build_detection_test_loader(cfg, dataset_name: str, batch_size: int = 1):
 
     def serial():
         for s in range(0, len(mine), batch_size):
-            yield [_test_record(cfg, d, datasets.to_mapper_input(d, fmt), dev) for d in mine[s:s + batch_size]]
+            yield [_test_record(cfg, d, datasets.to_mapper_input(d, fmt, is_train=False), dev) for d in mine[s:s + batch_size]]
 
     def ahead_of_time():
         ahead = prefetch.DecodeAhead(mine, lambda d: d["file_name"], workers,
@@ -155,7 +158,7 @@ def build_detection_test_loader(cfg, dataset_name: str, batch_size: int = 1):
                 got = ahead.take_planar(batch_size, fmt == "BGR")
                 if not got:
                     return
-                yield [_test_record(cfg, d, datasets.to_mapper_input(d, fmt, image=img), dev) for d, img in got]
+                yield [_test_record(cfg, d, datasets.to_mapper_input(d, fmt, image=img, is_train=False), dev) for d, img in got]
         finally:
             ahead.close()
     return serial() if workers == 0 else ahead_of_time()

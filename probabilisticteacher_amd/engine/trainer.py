@@ -321,14 +321,19 @@ class PTrainer:
 
     # ------------------------------------------------------------------ evaluation (trainer.py:127-137, 529-542)
     @classmethod
-    def build_evaluator(cls, cfg, class_names, is_2007: bool = False):
-        """trainer.py:127-137: TEST.EVALUATOR selects the evaluator; the VOC protocol ("VOCeval", the README's mAP50
-        tables) is implemented (probabilisticteacher_amd/evaluation.py); COCOeval needs pycocotools and is not."""
-        from ..evaluation import PascalVOCDetectionEvaluator
+    def build_evaluator(cls, cfg, class_names, is_2007: bool = False, dataset_dicts=None, output_dir=None):
+        """trainer.py:127-137: TEST.EVALUATOR selects the evaluator (probabilisticteacher_amd/evaluation.py).  "VOCeval": the
+        VOC protocol (the README's mAP50 tables).  "COCOeval" (the reference's default): the COCO protocol -- AP@[.5:.95], AP50,
+        AP75, APs / APm / APl, per-class AP -- restated without pycocotools, its matching step one HIP launch
+        (csrc/coco_eval.hip).  dataset_dicts: the registered dataset's dicts, from which the COCO evaluator reads its ground
+        truth as pycocotools reads the json (None: from the records, e.g. for an explicit data_loader); output_dir: where it
+        writes coco_instances_results.json.  Both work on COCO-format and on VOC-format datasets."""
+        from ..evaluation import COCODetectionEvaluator, PascalVOCDetectionEvaluator
         if cfg.TEST.EVALUATOR == "VOCeval":
             return PascalVOCDetectionEvaluator(class_names, is_2007=is_2007)
         if cfg.TEST.EVALUATOR == "COCOeval":
-            raise NotImplementedError("TEST.EVALUATOR=COCOeval needs pycocotools; use VOCeval")
+            return COCODetectionEvaluator(class_names, dataset_dicts=dataset_dicts, output_dir=output_dir,
+                                          device=torch.device(cfg.MODEL.DEVICE))
         raise ValueError("Unknown test evaluator.")
 
     @classmethod
@@ -347,7 +352,8 @@ class PTrainer:
     def test(cls, cfg, model, data_loader=None, class_names=None, is_2007: bool = False):
         """DefaultTrainer.test(cfg, model): eval-mode inference + the evaluator over every dataset of cfg.DATASETS.TEST
         (results keyed by dataset name when there are several, flat for one -- D2's convention), or over an explicit
-        `data_loader` of record batches with `class_names`.  Returns {"bbox": {"AP", "AP50", "AP75"}, ...}; on ranks other than
+        `data_loader` of record batches with `class_names`.  Returns {"bbox": {"AP", "AP50", "AP75"}, ...} (COCOeval: also APs,
+        APm, APl, AP-<class> and "bbox_recall"); on ranks other than
         0 of a multi-rank run the evaluator returns None (predictions are gathered on rank 0) and so does this."""
         from ..evaluation import inference_on_dataset
         amp = "bf16" if cfg.SOLVER.AMP.ENABLED else None
@@ -358,9 +364,11 @@ class PTrainer:
         results = {}
         for name in cfg.DATASETS.TEST:
             meta = datasets.metadata(name)
+            dicts = datasets.get_dataset_dicts([name]) if cfg.TEST.EVALUATOR == "COCOeval" else None
             with ops.operand_rounding(amp):
                 results[name] = inference_on_dataset(model, cls.build_test_loader(cfg, name),
-                                                     cls.build_evaluator(cfg, meta["thing_classes"], meta["year"] == 2007))
+                                                     cls.build_evaluator(cfg, meta["thing_classes"], meta.get("year") == 2007,
+                                                                         dataset_dicts=dicts))
         if len(results) == 1:
             results = list(results.values())[0]
         return results

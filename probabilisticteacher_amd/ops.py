@@ -1282,6 +1282,68 @@ def roi_infer_class_collect(sorted_keys, order, keep, keep_count, cls_seg, nimg:
     return dense, kept
 
 
+# ============================================================================ COCO evaluation (csrc/coco_eval.hip)
+COCO_MAX_DETS, COCO_MAX_THRESHOLDS, COCO_MAX_AREA_RANGES = 100, 16, 4
+
+
+def coco_match_max_gt() -> int:
+    """the largest ground-truth segment ptmi_coco_match serves"""
+    return int(_lib.load().ptmi_coco_match_max_gt())
+
+
+def coco_match(dt_xywh, dt_area, dt_off, gt_xywh, gt_area, gt_crowd, gt_off, iou_thr, area_rng, out=None):
+    """pycocotools computeIoU + evaluateImg over every (image, category) segment, threshold and area range in one launch
+    (ptmi_coco_match, which states the protocol).  dt_xywh (ND,4) / dt_area (ND) float64 in descending-score order per segment,
+    gt_xywh (NG,4) / gt_area (NG) float64, gt_crowd (NG) int32, dt_off / gt_off (S+1) int64, iou_thr (T) and area_rng (A,2)
+    float64.  Returns gt_ignore (A,NG), dt_match (A,T,ND), dt_ignore (A,T,ND), int32 (`out`: that triple, preallocated).
+    The offset tables are read back once to check that they tile the arrays and to size the launch: a segment of more than 100
+    detections or coco_match_max_gt() boxes, T > 16 or A > 4 is a ValueError before anything is launched."""
+    dev = dt_xywh.device
+    dt_xywh, dt_area = _chk(dt_xywh, torch.float64, "dt_xywh"), _chk(dt_area, torch.float64, "dt_area")
+    gt_xywh, gt_area = _chk(gt_xywh, torch.float64, "gt_xywh"), _chk(gt_area, torch.float64, "gt_area")
+    gt_crowd = _chk(gt_crowd, torch.int32, "gt_crowd")
+    iou_thr, area_rng = _chk(iou_thr, torch.float64, "iou_thr"), _chk(area_rng, torch.float64, "area_rng")
+    nd, ng, nthr, narea = dt_area.numel(), gt_area.numel(), iou_thr.numel(), area_rng.numel() // 2
+    if tuple(dt_xywh.shape) != (nd, 4) or tuple(gt_xywh.shape) != (ng, 4) or gt_crowd.numel() != ng \
+            or tuple(area_rng.shape) != (narea, 2) or iou_thr.dim() != 1:
+        raise ValueError("coco_match: expected dt_xywh (ND,4), dt_area (ND), gt_xywh (NG,4), gt_area (NG), gt_crowd (NG), "
+                         "iou_thr (T), area_rng (A,2)")
+    if not 1 <= nthr <= COCO_MAX_THRESHOLDS or not 1 <= narea <= COCO_MAX_AREA_RANGES:
+        raise ValueError(f"coco_match: {nthr} IoU thresholds / {narea} area ranges (at most {COCO_MAX_THRESHOLDS} / "
+                         f"{COCO_MAX_AREA_RANGES} are served)")
+    longest = []
+    for name, off, n in (("dt_off", dt_off, nd), ("gt_off", gt_off, ng)):
+        if off.dtype != torch.int64 or off.dim() != 1 or off.numel() != dt_off.numel() or off.numel() < 1:
+            raise ValueError(f"coco_match: {name} must be int64 (S+1), the same S for both tables")
+        host = off.detach().cpu()
+        lens = host[1:] - host[:-1]
+        if int(host[0]) != 0 or int(host[-1]) != n or (lens.numel() and int(lens.min()) < 0):
+            raise ValueError(f"coco_match: {name} does not tile its {n} rows")
+        longest.append(int(lens.max()) if lens.numel() else 0)
+    max_dt, max_gt = longest
+    if max_dt > COCO_MAX_DETS:
+        raise ValueError(f"coco_match: a segment holds {max_dt} detections (maxDets[-1] = {COCO_MAX_DETS}: keep the first "
+                         f"{COCO_MAX_DETS} by score)")
+    if max_gt > coco_match_max_gt():
+        raise ValueError(f"coco_match: a segment holds {max_gt} ground-truth boxes (at most {coco_match_max_gt()} are served)")
+    dt_off, gt_off = _chk(dt_off.to(dev), torch.int64, "dt_off"), _chk(gt_off.to(dev), torch.int64, "gt_off")
+    if out is None:
+        out = (torch.empty((narea, ng), dtype=torch.int32, device=dev),
+               torch.empty((narea, nthr, nd), dtype=torch.int32, device=dev),
+               torch.empty((narea, nthr, nd), dtype=torch.int32, device=dev))
+    gt_ignore, dt_match, dt_ignore = out
+    if tuple(gt_ignore.shape) != (narea, ng) or tuple(dt_match.shape) != (narea, nthr, nd) \
+            or tuple(dt_ignore.shape) != (narea, nthr, nd):
+        raise ValueError("coco_match: out = (gt_ignore (A,NG), dt_match (A,T,ND), dt_ignore (A,T,ND))")
+    for name, t in (("gt_ignore", gt_ignore), ("dt_match", dt_match), ("dt_ignore", dt_ignore)):
+        _chk(t, torch.int32, name)
+    with _prof("coco_match"):
+        _lib.call("ptmi_coco_match", _ptr(dt_xywh), _ptr(dt_area), _ptr(dt_off), _ptr(gt_xywh), _ptr(gt_area), _ptr(gt_crowd),
+                  _ptr(gt_off), dt_off.numel() - 1, nd, ng, max_dt, max_gt, _ptr(iou_thr), nthr, _ptr(area_rng), narea,
+                  _ptr(gt_ignore), _ptr(dt_match), _ptr(dt_ignore), _stream())
+    return gt_ignore, dt_match, dt_ignore
+
+
 # ============================================================================ losses (loss + gradient in one launch)
 class _BCELogitsSum(torch.autograd.Function):
     @staticmethod

@@ -9,7 +9,8 @@ Same flags as detectron2's default_argument_parser that the reference relies on 
 matching, --num-gpus, opts); process launch is torchrun-style (one process per GPU, RCCL).
 
 Data: by default the datasets named by cfg.DATASETS.TRAIN_LABEL / TRAIN_UNLABEL / TEST (VOC-format directories registered
-under $DETECTRON2_DATASETS as in pt/data/datasets/builtin.py, or ad hoc with --register NAME=DIR:SPLIT:CLASSES) go through
+under $DETECTRON2_DATASETS as in pt/data/datasets/builtin.py, or ad hoc with --register NAME=DIR:SPLIT:CLASSES; COCO-format
+jsons with --register-coco NAME=JSON:IMAGE_ROOT) go through
 the host decoder + device two-crop mapper + aspect-ratio grouping (probabilisticteacher_amd/data, reference
 pt/data/build.py:107-217); `--synthetic` feeds seeded synthetic two-crop batches in the same record format instead."""
 import argparse
@@ -47,6 +48,8 @@ def main():
                     help="log the losses only, without the rpn/ roi_head/ fast_rcnn/ statistics of a reference run's metrics.json")
     ap.add_argument("--register", action="append", default=[], metavar="NAME=DIR:SPLIT:CLS1,CLS2",
                     help="register a VOC-format directory as dataset NAME (Annotations/, JPEGImages/, ImageSets/Main/SPLIT.txt)")
+    ap.add_argument("--register-coco", action="append", default=[], metavar="NAME=JSON:IMAGE_ROOT",
+                    help="register a COCO-format json (images under IMAGE_ROOT) as dataset NAME")
     ap.add_argument("opts", nargs=argparse.REMAINDER)
     args = ap.parse_args()
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("LOCAL_RANK", 0), ("WORLD_SIZE", 1)))
@@ -63,6 +66,10 @@ def main():
         name, rest = spec.split("=", 1)
         dirname, split, classes = rest.split(":")
         datasets.register_pascal_voc(name, dirname, split, tuple(classes.split(",")))
+    for spec in args.register_coco:
+        name, rest = spec.split("=", 1)
+        json_file, image_root = rest.split(":")
+        datasets.register_coco_instances(name, json_file, image_root)
     from probabilisticteacher_amd.seeding import seed_all_rng
     seed_all_rng(None if cfg.SEED < 0 else cfg.SEED + rank)    # D2 default_setup
     if cfg.SEED < 0:
