@@ -510,10 +510,23 @@ __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
             }
             if constexpr (S == XHAND) {
                 // everything but this chunk's DMA instructions so far (11 of its 12) has landed: slab c + 1, patch c + 2
-                if (!skipwait) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(x_dma_before(XHAND)) : "memory");   // [x4:ho]
+                if (!skipwait) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(x_dma_before(XHAND)) : "memory");   // [x4:ho] [x4:hov]
                 skipwait = false;
-                fixup(pf, fix_ho, edge_ho);   // [x4:ho]
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // [x4:ho]
+                // fix-ups of that patch.  edge_ho is wave-uniform: a scalar branch of its own, so that only a chunk whose patch
+                // straddles an image's right edge pays the per-lane mask test (merged into one exec mask -- what the compiler makes
+                // of `edge_ho && fix_ho`, and the empty asm prevents -- every chunk paid a v_cmp -> s_and_saveexec round trip between
+                // two MFMAs: 1.5 - 2.5 % of the layer, profiles/handover_per_layer.txt)
+                if (edge_ho) {   // [x4:ho] [x4:hof]
+                    asm volatile("" ::: "memory");   // [x4:ho] [x4:hof]
+                    fixup(pf, fix_ho, true);   // [x4:ho] [x4:hof]
+                }   // [x4:ho] [x4:hof]
+                // The drain is lgkmcnt(0), not a counted wait: the newest LDS reads in flight here are the A reads of slots 65 and 67
+                // (groups 18, 19 of THIS chunk's slab stage uo0 -- the ds_read_b64 pair in front of the wait in the ISA), and uo0 is
+                // what the barrier hands to the next chunk's DMA: N = 0 LDS operations follow the last read of a freed stage.  (The
+                // reads of the next chunk's groups 0, 1 through apn sit in slots 69 and 71, behind the barrier: they need slab c + 1
+                // published.)  Measured, the drain costs nothing: profiles/handover_stamps.txt
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // [x4:ho] [x4:hol]
+                asm volatile("s_barrier" ::: "memory");   // [x4:ho] [x4:hob]
             }
             constexpr int wr = x_wread_at(S);
             if constexpr (wr >= 0) wread(std::integral_constant<int, (wr >= 0 ? wr : 0)>{}, pb, pe);   // [x4:wr]

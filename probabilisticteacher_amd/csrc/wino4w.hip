@@ -21,8 +21,8 @@
 //     fall on 16 distinct 16-byte bank groups.
 //   * three LDS stages of 40 KB (64 dY planes of 4 x 16 pixels, 32 x planes of 6 x 24), `buffer_load_dwordx4 ... lds`, ten DMA
 //     instructions per lane and chunk issued five per k-step, one and a half chunks ahead; ONE workgroup barrier per chunk behind
-//     a counted vmcnt(5); interior chunks use the lane's loop-invariant offsets, border chunks mask them by per-lane validity
-//     bits built once; the descriptor bases advance by a step per chunk.
+//     a counted vmcnt (the hand-over: slots ZFIX / ZHAND below); interior chunks use the lane's loop-invariant offsets, border
+//     chunks mask them by per-lane validity bits built once; the descriptor bases advance by a step per chunk.
 //   * partial dU go to the workspace [split][position 36][co][ci]; the bias gradient (sum of dY) is accumulated by the row-(0,+a,-a)
 //     waves on every ciTiles-th chunk (each (co tile, ci tile) pair a different residue: together every chunk once) and appended
 //     as [split][ci tile][co]; wino4_wgrad_reduce sums splits in a fixed order (deterministic) and applies G^T . G.
@@ -131,14 +131,56 @@ __device__ __forceinline__ void zfor(std::integer_sequence<int, I...>, F&& f) { 
 
 // ---- the k-step schedule: 18 slots (MFMA q on the current operands + its share of the NEXT k-step's operands)
 //   slots 0 .. 6: the 19 raw reads (three per slot: dY rows 0 .. 3, then the five window rows x three parts)
-//   slot 7 of a chunk's first k-step: the hand-over for the next chunk
+//   slots ZFIX, ZHAND of a chunk's first k-step: the hand-over for the next chunk
 //   slots 8, 10, .., 16: one DMA instruction each
 //   slots 2 .. 17: the 112 transform FMAs, seven per slot: 0 .. 39 W (vertical 16, horizontal 24), 40 .. 75 V vertical, 76 .. 111 V horizontal
 //   (reads four per slot and the FMAs from slot 6 on -- five slots behind the reads they consume -- measured 2 % SLOWER: the reads' cost
 //   is not latency)
-constexpr int ZHAND = 7;
 __host__ __device__ constexpr int z_dma_at(int s) { return (s >= 8 && s <= 16 && !(s & 1)) ? (s - 8) / 2 : -1; }
 __host__ __device__ constexpr int z_valu_before(int s) { return s < 2 ? 0 : ((s - 2) * 7 > 112 ? 112 : (s - 2) * 7); }
+constexpr int ZRAW_LAST = 6;            // the slot of the k-step's last raw read
+// The hand-over, in two slots of a chunk's first k-step.  ZFIX: the counted vmcnt wait for the next chunk's data and the fix-up
+// stores into it.  ZHAND: the drain of the wave's LDS operations and the barrier.  The stage the barrier frees (s_cur) is a DMA
+// target from the NEXT k-step on, and the stage it publishes (s_nxt) is read from the next k-step on, so any slots behind the last
+// raw read of this k-step serve.  Every DMA slot ZFIX passes adds one instruction that may stay in flight (z_hand_vmcnt).
+// The two parts in one slot, measured at 7 / 9 / 11 / 13 / 15: 9 is the fastest, and the later ones lose again.  Two slots apart,
+// the fix-up stores of a last-column chunk complete under the MFMAs in between instead of in front of the barrier (profiles/
+// handover_per_layer.txt, profiles/handover_stamps.txt).  The macros are for such sweeps (tools/exp/make_wino4_variant.py).
+#ifndef W4W_FIX_SLOT
+#define W4W_FIX_SLOT 9
+#endif
+#ifndef W4W_HAND_SLOT
+#define W4W_HAND_SLOT 11
+#endif
+constexpr int ZHAND = W4W_HAND_SLOT, ZFIX = W4W_FIX_SLOT;
+// DMA instructions in flight that the wait in slot `fix` leaves alone: the previous k-step's (the first half of chunk c + 2) and
+// this k-step's issued in the slots before it (a slot's DMA instruction follows the slot's hand-over)
+__host__ __device__ constexpr int z_hand_vmcnt(int fix)
+{
+    int n = ZNP / 2;
+    for (int s = 0; s < fix; ++s) n += z_dma_at(s) >= 0;
+    return n;
+}
+static_assert(ZFIX > ZRAW_LAST && ZFIX <= ZHAND && ZHAND < 18,
+              "wino4w: the hand-over lies behind the last raw read of s_cur, inside the first k-step");
+static_assert(z_hand_vmcnt(7) == 5 && z_hand_vmcnt(9) == 6 && z_hand_vmcnt(17) == 10, "wino4w: five DMA instructions per k-step");
+
+// the most DMA pieces of ONE lane that lie at the same patch column q4 (dY pieces at column q4 and x pieces at column q4; q4 = 16: the x
+// patch's halo pieces alone) -- what the fix-up offsets of a lane have to hold (below)
+__host__ __device__ constexpr int z_pieces_at_column(int q4)
+{
+    int most = 0;
+    for (int tid = 0; tid < ZNT; ++tid) {
+        int n = 0;
+        for (int i = 0; i < ZNP; ++i) {
+            const int p = tid + (i < ZND ? i : i - ZND) * ZNT;
+            if (i < ZND) n += p < ZC * ZDPC && p % ZDPC < 16 && 4 * (p % ZDPC & 3) == q4;
+            else n += p < ZI * ZXPC && p % ZXPC < 36 && 4 * (p % ZXPC % 6) - 4 == q4;
+        }
+        most = n > most ? n : most;
+    }
+    return most;
+}
 
 template <int PH>
 __device__ __forceinline__ void wino4_wgrad_body(
@@ -164,14 +206,32 @@ __device__ __forceinline__ void wino4_wgrad_body(
     // border combines them with wave-uniform selects.  The classes, each an independent flag:
     //   first column block: the left halo pieces (x, column -4) are out;  last: pieces from column wl on;  top tile row: window row
     //   y0 - 1;  bottom (= last) tile row: rows from hb on.  The x patch reaches column x0 + 19, so when the last block is narrower than
-    //   four columns the second-to-last block's right halo piece straddles the edge too: it stays valid and only gets fix-up bits.
+    //   four columns the second-to-last block's right halo piece straddles the edge too: it stays valid and only gets fix-ups.
     const int wl = W - (colBlocks - 1) * 16;             // width of the last column block (1 .. 16)
     const int hb = H - (tileRows - 1) * 4;               // rows of the last tile row (1 .. 4)
     const int cbLast2 = wl < 4 ? colBlocks - 2 : -1;     // the column block before the last, where its halo straddles (-1: none such)
+    // Fix-ups: a 16-byte piece that the image's right edge cuts is fetched whole, and its words past the edge (the next row's first
+    // pixels) are zeroed in LDS by the lane that fetched it (whose counted vmcnt wait covers it).  Which words is wave-uniform: in
+    // the last column block the pieces at column fq of both patches, words fe .. 3; in the second-to-last one (wl < 4 only) the x
+    // patch's halo pieces at column 16, words wl .. 3.  Which of its ten pieces those are differs per lane, but never changes: at most
+    // ZF1 / ZF2 of them (two of a lane's five dY pieces, three of its five x pieces, for every residue of tid), kept as LDS offsets
+    // with the lane's own word of the dY region's padding (pieces ZC * ZDPC ..: zero fill, read by nobody) standing in for "none".
+    // The stores then need no per-lane test at all.  The offsets (< 2^16 floats) are packed two to a register and unpacked where a
+    // chunk of those classes uses them.  (Thirty exec-masked tests over per-lane bit masks, as before, cost a chunk of
+    // those classes a third of its time: 2 - 3.5 % of the layer, profiles/handover_stamps.txt.)
+    constexpr int ZF1 = 5, ZF2 = 3;
+    static_assert(z_pieces_at_column(0) <= ZF1 && z_pieces_at_column(4) <= ZF1 && z_pieces_at_column(8) <= ZF1 && z_pieces_at_column(12) <= ZF1 &&
+                  z_pieces_at_column(16) <= ZF2, "wino4w: a lane's fix-up offsets");
+    const int fq = (wl - 1) & ~3;
+    const int fe = wl - fq;                              // 1 .. 3; 4: the image ends on a piece boundary, nothing to fix
+    int fo1[ZF1], fo2[ZF2], nf1 = 0, nf2 = 0;
+#pragma unroll
+    for (int k = 0; k < ZF1; ++k) fo1[k] = ZC * ZDPC * 4 + lane;
+#pragma unroll
+    for (int k = 0; k < ZF2; ++k) fo2[k] = ZC * ZDPC * 4 + lane;
     unsigned voff[ZNP];
     unsigned inv_a = 0;                                  // pieces out in the first block (bits 0 .. 9) / the last (10 .. 19) / the top row (20 .. 29)
     unsigned inv_b = 0;                                  // pieces out in the bottom row (bits 0 .. 9) / channel outside the tensor or pad (10 .. 19)
-    unsigned long long fix_last = 0, fix_last2 = 0;      // last / second-to-last column block: words past the image edge, bits 4 i + e
 #pragma unroll
     for (int i = 0; i < ZNP; ++i) {
         bool chok; int ch, r, q4, lev;                   // plane row / first column / row relative to y0 of piece i
@@ -192,14 +252,20 @@ __device__ __forceinline__ void wino4_wgrad_body(
         inv_a |= (unsigned)(q4 < 0) << i | (unsigned)(q4 >= wl) << (10 + i) | (unsigned)(lev < 0) << (20 + i);
         inv_b |= (unsigned)(lev >= hb) << i | (unsigned)!chok << (10 + i);
         // (a piece whose row is masked needs no fix-up, and gets one all the same: zeroing zeros is harmless)
-        if (chok) {
+        const int lo = i < ZND ? (tid + i * ZNT) * 4 : ZDR + (tid + (i - ZND) * ZNT) * 4;   // the piece in a stage
+        const bool hit1 = chok && q4 == fq, hit2 = chok && q4 == 16;
 #pragma unroll
-            for (int e = 1; e < 4; ++e) {
-                fix_last |= (q4 < wl && q4 + e >= wl) ? (1ull << (4 * i + e)) : 0ull;
-                fix_last2 |= (q4 + e >= wl + 16) ? (1ull << (4 * i + e)) : 0ull;
-            }
-        }
+        for (int k = 0; k < ZF1; ++k) fo1[k] = (hit1 && nf1 == k) ? lo : fo1[k];
+#pragma unroll
+        for (int k = 0; k < ZF2; ++k) fo2[k] = (hit2 && nf2 == k) ? lo : fo2[k];
+        nf1 += hit1;
+        nf2 += hit2;
     }
+    static_assert(ZSTAGE < (1 << 16) && (ZF1 + ZF2) % 2 == 0, "wino4w: two fix-up offsets per register");
+    unsigned fpk[(ZF1 + ZF2) / 2];                       // halves 0 .. ZF1 - 1: last column block; the rest: second-to-last
+#pragma unroll
+    for (int k = 0; k < ZF1 + ZF2; k += 2)
+        fpk[k / 2] = (unsigned)(k < ZF1 ? fo1[k] : fo2[k - ZF1]) | (unsigned)(k + 1 < ZF1 ? fo1[k + 1] : fo2[k + 1 - ZF1]) << 16;
     // records of a descriptor: the bytes from its base to the tensor's end, clamped to [0, 2^32 - 2] -- a fetch never reaches past the
     // tensor (on the 32-bit halves: 64-bit compares would go to the VALU)
     auto clamp_rec = [](long long rem) __attribute__((always_inline)) {
@@ -208,7 +274,7 @@ __device__ __forceinline__ void wino4_wgrad_body(
         return (int)(hi < 0 ? 0u : ((hi > 0 || lo > 0xFFFFFFFEu) ? 0xFFFFFFFEu : lo));
     };
 
-    // ---- the fetch in progress: descriptors, effective per-piece offsets, fix-up masks (current and previous set-up)
+    // ---- the fetch in progress: descriptors, effective per-piece offsets, fix-up classes (current and previous set-up)
     int f_cb, f_ty;                                      // column block / tile row of the NEXT chunk to set up
     // ... and its two patch origins as byte offsets from x / dy: x (y0 - 1, x0 - 4) of channel ci0, dY (y0, x0) of channel co0 (the
     // first chunk's x origin lies before the tensor).  Advanced chunk by chunk -- 16 floats per column block, a row step and an image
@@ -238,17 +304,17 @@ __device__ __forceinline__ void wino4_wgrad_body(
 #pragma unroll
     for (int i = 0; i < ZNP; ++i) eoff[i] = voff[i];
     unsigned e_cls = 0;                                  // the class eoff stands for (0: interior = voff)
-    unsigned long long fix = 0, fix_prev = 0;            // words past the image edge, bits 4 i + e (current and previous set-up)
+    const unsigned fixable = (fe < 4 ? Z_LAST : 0u) | Z_LAST2;
+    unsigned fix_cls = 0, fix_cls_prev = 0;              // (wave-uniform) the class bits with words to fix (current and previous set-up)
     auto fetch_setup = [&]() __attribute__((always_inline)) {
         rx = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr((const char*)x + xo), 0, clamp_rec(x_bytes - xo), 0x00020000);
         rd = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr((const char*)dy + dO), 0, clamp_rec(dy_bytes - dO), 0x00020000);
-        fix_prev = fix;
+        fix_cls_prev = fix_cls;
         // class 0 = interior chunk: every row and column of both patches inside the image -- the loop-invariant offsets serve
         const unsigned cls = f_left > 0 ? (f_cb == 0 ? Z_FIRST : 0u) | (f_cb == colBlocks - 1 ? Z_LAST : 0u) | (f_cb == cbLast2 ? Z_LAST2 : 0u) |
                                               (f_ty == 0 ? Z_TOP : 0u) | (f_ty == tileRows - 1 ? Z_BOT : 0u)
                                         : Z_NONE;
-        fix = 0;
-        if (cls & (Z_LAST | Z_LAST2)) fix = (cls & Z_LAST) ? fix_last : fix_last2;
+        fix_cls = cls & fixable;
         if (cls != e_cls) {
             e_cls = cls;
             if (cls == 0) {
@@ -276,14 +342,18 @@ __device__ __forceinline__ void wino4_wgrad_body(
         zlds_void_t* dst = (zlds_void_t*)(lds + stage * ZSTAGE + (idx < ZND ? wave * 256 + idx * ZNT * 4 : ZDR + wave * 256 + (idx - ZND) * ZNT * 4));
         __builtin_amdgcn_raw_ptr_buffer_load_lds(idx < ZND ? rd : rx, dst, 16, (int)eoff[idx], 0, 0, 0);
     };
-    auto fixup = [&](int stage, unsigned long long fm) __attribute__((always_inline)) {
-        if ((unsigned)fm | (unsigned)(fm >> 32)) {
+    auto fixup = [&](int stage, unsigned fcls) __attribute__((always_inline)) {   // fcls: Z_LAST or Z_LAST2
+        float* const st = lds + stage * ZSTAGE;
+        const int k0 = (fcls & Z_LAST) ? 0 : ZF1, k1 = (fcls & Z_LAST) ? ZF1 : ZF1 + ZF2, e0 = (fcls & Z_LAST) ? fe : wl;
 #pragma unroll
-            for (int i = 0; i < ZNP; ++i) {
-                float* pc = lds + stage * ZSTAGE + (i < ZND ? (tid + i * ZNT) * 4 : ZDR + (tid + (i - ZND) * ZNT) * 4);
+        for (int k = 0; k < ZF1 + ZF2; ++k) {
+            if (k >= k0 && k < k1) {
+                unsigned pk = fpk[k / 2];
+                asm volatile("" : "+v"(pk));             // (unpacked here, not hoisted out of the chunk loop into registers of its own)
+                const int fo = (k & 1) ? pk >> 16 : pk & 0xFFFFu;
 #pragma unroll
                 for (int e = 1; e < 4; ++e)
-                    if (fm & (1ull << (4 * i + e))) pc[e] = 0.f;
+                    if (e >= e0) st[fo + e] = 0.f;
             }
         }
     };
@@ -365,12 +435,12 @@ __device__ __forceinline__ void wino4_wgrad_body(
         fetch_setup();
 #pragma unroll
         for (int idx = 0; idx < ZNP; ++idx) fetch_piece(idx, 1);
-        const unsigned long long fix0 = fix_prev;
+        const unsigned fix0 = fix_cls_prev;
         fetch_setup();
 #pragma unroll
         for (int idx = 0; idx < 5; ++idx) fetch_piece(idx, 2);
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ZNP + 5) : "memory");
-        fixup(0, fix0);
+        if (fix0) fixup(0, fix0);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         // operands of (chunk 0, k-step 0)
         zfor(std::make_integer_sequence<int, 19>{}, [&](auto k_c) __attribute__((always_inline)) { raw_read(k_c, lds, 0); });
@@ -404,12 +474,18 @@ __device__ __forceinline__ void wino4_wgrad_body(
                         raw_read(std::integral_constant<int, 3 * Q + decltype(r_c)::value>{}, src, ks8);   // [x4:rd]
                     });
                 }
+                if constexpr (Q == ZFIX && KS == 0) {
+                    // hand-over, first part: everything but the newest DMA instructions (chunk c + 2's so far) has landed, i.e.
+                    // chunk c + 1; fix-ups.  Only a chunk in the last / second-to-last column block has words to fix: a
+                    // wave-uniform property, so every other chunk passes with one scalar branch
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(z_hand_vmcnt(ZFIX)) : "memory");   // [x4:ho] [x4:hov]
+                    if (fix_cls_prev) fixup(s_nxt, fix_cls_prev);   // [x4:ho] [x4:hof]
+                }
                 if constexpr (Q == ZHAND && KS == 0) {
-                    // hand-over: everything but the five newest DMA instructions (the first half of chunk c + 2) has landed, i.e.
-                    // chunk c + 1; fix-ups; barrier -- then stage s_cur is free (its last raw reads were this k-step's)
-                    asm volatile("s_waitcnt vmcnt(5)" ::: "memory");   // [x4:ho]
-                    fixup(s_nxt, fix_prev);   // [x4:ho]
-                    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // [x4:ho]
+                    // ... second part: the drain (the wave's raw reads of s_cur and, where there were any, the fix-up stores) and the
+                    // barrier -- then stage s_cur is free (its last raw reads were this k-step's) and chunk c + 1 is everyone's to read
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // [x4:ho] [x4:hol]
+                    asm volatile("s_barrier" ::: "memory");   // [x4:ho] [x4:hob]
                 }
                 constexpr int di = z_dma_at(Q);
                 if constexpr (di >= 0) fetch_piece(KS == 0 ? 5 + di : di, st_dma);   // [x4:dma]

@@ -6,7 +6,9 @@
     (on the GPU box)  python tools/exp/wino4_bench.py --only4 --lib tools/exp/_bin/libptmi355_w4_noxf.so --layers conv3_2
 
 parts: mf = the MFMAs, xf = the input transforms' FMAs, wr = window reads, ar = A-operand reads, dma = the LDS-DMA instructions,
-ho = the hand-over (counted vmcnt, fix-ups, barrier).  W4FILE=wino4w: the weight-gradient kernel (parts mf, xf, rd = raw operand
+ho = the hand-over (counted vmcnt, fix-ups, barrier) -- in wino4p / wino4w also one at a time: hov = the counted vmcnt wait,
+hof = the fix-up test and body, hol = the lgkmcnt drain, hob = the barrier.  Leading options go to hipcc (the product's
+-fno-slp-vectorize; -DW4W_HAND_SLOT=<slot> for the weight gradient's hand-over slot).  W4FILE=wino4p: csrc/wino4p.hip; W4FILE=wino4w: the weight-gradient kernel (parts mf, xf, rd = raw operand
 reads, dma, ho) -> libptmi355_w4w_<name>.so.  The `else` of a removed `if constexpr` pair goes with it."""
 import os
 import subprocess
