@@ -626,6 +626,9 @@ __global__ void wino_pack_weights_kernel(const float* __restrict__ w, float* __r
 //     64 x 4 x 40 of x) four per k-step during the last two k-steps of chunk c - 2 and the first two of chunk c - 1; LDS reads
 //     run two k-steps ahead of the MFMAs and the transforms one, so the chunk hand-over (vmcnt(0), edge fix-ups, barrier) sits at
 //     k-step 6 of 8 with every own read four k-steps old.
+//   * the chunk set-up is wino4w.hip's: patch origins stepped chunk by chunk, one offsets array rewritten when the chunk's border
+//     class changes, fix-up stores from per-lane LDS offsets built once (every SALU or VALU instruction in the loop costs the lone
+//     wave of a SIMD issue time).
 constexpr int GWC = 64;                  // channels per operand tile
 // geometry of a chunk of KSN k-steps (= 2 KSN tiles = 4 KSN columns of one tile row).  KSN = 8: 32 columns; KSN = 7: 28 columns,
 // which tiles W = 83 / 166 / 333 (21 / 42 / 84 tile pairs per row) without the 12.5 / 12.5 / 4.5 % of padded k-steps of KSN = 8
@@ -643,6 +646,26 @@ template <int KSN> struct WG {
     static constexpr int GXR = GNX * 1024;
     static constexpr int GSTAGE = GDYR + GXR;        // 64 KB / 56 KB; two stages
 };
+
+// the most DMA pieces of ONE lane that lie at the same patch column (x pieces at column q4 and dY pieces at column q4) -- what the
+// fix-up offsets of a lane have to hold (in the kernel)
+template <int KSN> __host__ __device__ constexpr int wg_pieces_at_column()
+{
+    using G = WG<KSN>;
+    int most = 0;
+    for (int q4 = 0; q4 < G::COLS; q4 += 4)
+        for (int tid = 0; tid < WNT; ++tid) {
+            int n = 0;
+            for (int i = 0; i < G::NP; ++i) {
+                const int p = tid + (i < G::GNX ? i : i - G::GNX) * WNT;
+                if (i < G::GNX) n += p < GWC * G::XPC && p % G::XPC < 4 * G::XPR && 4 * (p % G::XPC % G::XPR) - 4 == q4;
+                else n += p < GWC * G::DPC && p % G::DPC < 2 * KSN && 4 * (p % G::DPC % KSN) == q4;
+            }
+            most = n > most ? n : most;
+        }
+    return most;
+}
+constexpr int WGF = 6;                   // fix-up offsets per lane: four x pieces and one dY piece at the most, rounded up to a pair
 
 template <int KSN>
 __global__ __launch_bounds__(WNT, 1) void conv3x3_wino_wgrad_kernel(
@@ -666,107 +689,145 @@ __global__ __launch_bounds__(WNT, 1) void conv3x3_wino_wgrad_kernel(
     const int nC = max(min(cBegin + per, nChunksAll) - cBegin, 0);
 
     // ---- per-lane DMA pieces (fetch order: 11 of x, then 5 of dY), relative to the chunk's origin: x (y0 - 1, x0 - 4), dY (y0, x0).
-    // Validity is (channel) & (column, by the class of the column block: first / interior / last) & (row, by the tile row):
-    // bit masks over the lane's 16 pieces, built once; a chunk combines them with a handful of wave-uniform selects.
-    unsigned voff[GNX + GND];
-    unsigned m_ch = 0, m_first = 0, m_last = 0;          // channel inside the tensor; column valid in the first / last column block
-    unsigned m_r0 = 0, m_r2 = 0, m_r3 = 0, m_d1 = 0;     // x pieces of window row 0 / 2 / 3, dY pieces of row 1
-    unsigned long long fix_last = 0;                     // last column block: words past the image edge, bits 4 i + e
+    // A piece is fetched iff (channel) & (column, by the class of the column block: first / interior / last) & (row, by the class of
+    // the tile row: top / interior / bottom).  All of it is loop-invariant per lane, so it is built once, as bit masks over the lane's
+    // 16 pieces (as wino4w.hip); a chunk on the image border combines them with wave-uniform selects.  The x patch's right halo piece
+    // (column x0 + 4 KSN) is read in its first word only, which every block before the last has inside the image (wvl >= 1).
+    constexpr int NP = GNX + GND;
+    static_assert(NP <= 16, "wino wgrad: two 16-bit piece masks per register");
+    unsigned voff[NP];
+    unsigned inv_col = 0;                                // pieces out in the first column block (bits 0 .. 15) / the last (16 .. 31)
+    unsigned inv_row = 0;                                // pieces out in the top tile row (bits 0 .. 15) / the bottom one (16 .. 31)
     const int wvl = W - (colBlocks - 1) * G::COLS;       // width of the last column block (1 .. 4 KSN)
+    const bool hOdd = H & 1;                             // the bottom tile row holds one image row (else two)
+    // Fix-ups: a 16-byte piece that the image's right edge cuts is fetched whole, and its words past the edge (the next row's first
+    // pixels) are zeroed in LDS by the lane that fetched it.  Which words is wave-uniform: in the last column block the pieces at
+    // column fq of both patches, words fe .. 3.  Which of its 16 pieces those are differs per lane, but never changes: at most WGF of
+    // them (wg_pieces_at_column), kept as LDS offsets with the lane's own word of the dY region's padding (pieces GWC * DPC ..: zero
+    // fill, read by nobody) standing in for "none", packed two to a register.  The stores then need no per-lane test at all.
+    static_assert(wg_pieces_at_column<KSN>() <= WGF && WGF % 2 == 0 && GSTAGE < (1 << 16), "wino wgrad: a lane's fix-up offsets");
+    static_assert(GDYR - GWC * G::DPC * 4 >= 64 + 3, "wino wgrad: the pad words of a wave's lanes");
+    const int fq = (wvl - 1) & ~3;
+    const int fe = wvl - fq;                             // 1 .. 3; 4: the image ends on a piece boundary, nothing to fix
+    int fo[WGF], nf = 0;
 #pragma unroll
-    for (int i = 0; i < GNX; ++i) {
-        const int px = tid + i * WNT;
-        const int ch = px / G::XPC, rem = px - ch * G::XPC;
-        const int r = rem / G::XPR, q4 = 4 * (rem - r * G::XPR) - 4;
-        const bool ok = px < GWC * G::XPC && rem < 4 * G::XPR && ci0 + ch < Cin;
-        voff[i] = ok ? (unsigned)(ch * HW + r * W + q4 + 4) * 4u : 0xFFFFFFFFu;
-        m_ch |= (unsigned)ok << i;
-        m_first |= (unsigned)(q4 >= 0) << i;
-        m_last |= (unsigned)(q4 < wvl) << i;
-        m_r0 |= (unsigned)(r == 0) << i;
-        m_r2 |= (unsigned)(r == 2) << i;
-        m_r3 |= (unsigned)(r == 3) << i;
-        if (ok && q4 < wvl && q4 + 4 > wvl)
-            for (int e = 1; e < 4; ++e) fix_last |= (q4 + e >= wvl) ? (1ull << (4 * i + e)) : 0ull;
-    }
+    for (int k = 0; k < WGF; ++k) fo[k] = GWC * G::DPC * 4 + lane;
 #pragma unroll
-    for (int i = 0; i < GND; ++i) {
-        const int pd = tid + i * WNT;
-        const int ch = pd / G::DPC, rem = pd - ch * G::DPC;
-        const int r = rem / KSN, q4 = 4 * (rem - r * KSN);
-        const bool ok = pd < GWC * G::DPC && rem < 2 * KSN && co0 + ch < Cout;
-        voff[GNX + i] = ok ? (unsigned)(ch * HW + r * W + q4) * 4u : 0xFFFFFFFFu;
-        m_ch |= (unsigned)ok << (GNX + i);
-        m_first |= 1u << (GNX + i);
-        m_last |= (unsigned)(q4 < wvl) << (GNX + i);
-        m_d1 |= (unsigned)(r == 1) << (GNX + i);
-        if (ok && q4 < wvl && q4 + 4 > wvl)
-            for (int e = 1; e < 4; ++e) fix_last |= (q4 + e >= wvl) ? (1ull << (4 * (GNX + i) + e)) : 0ull;
+    for (int i = 0; i < NP; ++i) {
+        bool ok; int ch, r, q4, lo;                      // channel inside the tensor / plane / row / first column / place in a stage
+        if (i < GNX) {
+            const int px = tid + i * WNT;
+            ch = px / G::XPC;
+            const int rem = px - ch * G::XPC;
+            r = rem / G::XPR; q4 = 4 * (rem - r * G::XPR) - 4;
+            ok = px < GWC * G::XPC && rem < 4 * G::XPR && ci0 + ch < Cin;
+            lo = GDYR + px * 4;
+            inv_row |= (unsigned)(r == 0) << i | (unsigned)(r == 3 || (hOdd && r == 2)) << (16 + i);
+        } else {
+            const int pd = tid + (i - GNX) * WNT;
+            ch = pd / G::DPC;
+            const int rem = pd - ch * G::DPC;
+            r = rem / KSN; q4 = 4 * (rem - r * KSN);
+            ok = pd < GWC * G::DPC && rem < 2 * KSN && co0 + ch < Cout;
+            lo = pd * 4;
+            inv_row |= (unsigned)(hOdd && r == 1) << (16 + i);
+        }
+        voff[i] = ok ? (unsigned)(ch * HW + r * W + q4 + (i < GNX ? 4 : 0)) * 4u : 0xFFFFFFFFu;
+        inv_col |= (unsigned)(q4 < 0) << i | (unsigned)(q4 >= wvl) << (16 + i);
+        // (a piece whose row is masked needs no fix-up, and gets one all the same: zeroing zeros is harmless)
+        const bool hit = ok && q4 == fq;
+#pragma unroll
+        for (int k = 0; k < WGF; ++k) fo[k] = (hit && nf == k) ? lo : fo[k];
+        nf += hit;
     }
-    const char* x_end = (const char*)(x + (size_t)N * Cin * HW);
-    const char* dy_end = (const char*)(dy + (size_t)N * Cout * HW);
-    auto clamp_rec = [](long long rem) { return (int)(rem > 0xFFFFFFFEll ? 0xFFFFFFFEll : (rem < 0 ? 0 : rem)); };
+    unsigned fpk[WGF / 2];
+#pragma unroll
+    for (int k = 0; k < WGF; k += 2) fpk[k / 2] = (unsigned)fo[k] | (unsigned)fo[k + 1] << 16;
+    // records of a descriptor: the bytes from its base to the tensor's end, clamped to [0, 2^32 - 2] -- a fetch never reaches past the
+    // tensor (on the 32-bit halves: 64-bit compares would go to the VALU)
+    auto clamp_rec = [](long long rem) __attribute__((always_inline)) {
+        const int hi = (int)(rem >> 32);
+        const unsigned lo = (unsigned)rem;
+        return (int)(hi < 0 ? 0u : ((hi > 0 || lo > 0xFFFFFFFEu) ? 0xFFFFFFFEu : lo));
+    };
 
-    // ---- the fetch in progress: descriptors, effective per-piece offsets, fix-up mask
-    int f_cb, f_ty, f_n;                                 // coordinates of the NEXT chunk to set up
+    // ---- the fetch in progress: descriptors, effective per-piece offsets, fix-up flag
+    int f_cb, f_ty;                                      // column block / tile row of the NEXT chunk to set up
+    // ... and its two patch origins as byte offsets from x / dy: x (y0 - 1, x0 - 4) of channel ci0, dY (y0, x0) of channel co0 (the
+    // first chunk's x origin lies before the tensor).  Advanced chunk by chunk -- one column block, a row step and an image step at
+    // the wraps -- instead of rebuilt from the coordinates with 64-bit multiplies: every SALU instruction in the loop costs the lone
+    // wave of a SIMD issue time, as a VALU one does
+    long long xo, dO;
     {
         const int g = min(cBegin, max(nChunksAll - 1, 0));
         f_cb = g % colBlocks;
         const int t = g / colBlocks;
         f_ty = t % tilesY2;
-        f_n = t / tilesY2;
+        const int f_n = t / tilesY2;
+        xo = (((long long)f_n * Cin + ci0) * HW + ((long long)2 * f_ty - 1) * W + (f_cb * G::COLS - 4)) * 4;
+        dO = (((long long)f_n * Cout + co0) * HW + (long long)2 * f_ty * W + f_cb * G::COLS) * 4;
     }
     int f_left = nC;                                     // chunks of this split not yet set up
+    const long long x_bytes = (long long)N * Cin * HW * 4, dy_bytes = (long long)N * Cout * HW * 4;
+    const long long stepRow = ((long long)2 * W - G::COLS * (colBlocks - 1)) * 4;
+    const long long stepImgX = ((long long)Cin * HW - (long long)2 * (tilesY2 - 1) * W - G::COLS * (colBlocks - 1)) * 4;
+    const long long stepImgD = ((long long)Cout * HW - (long long)2 * (tilesY2 - 1) * W - G::COLS * (colBlocks - 1)) * 4;
     __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr(x), 0, 0, 0x00020000);
     __amdgpu_buffer_rsrc_t rd = rx;
-    unsigned eoff[GNX + GND];                            // effective offsets of a chunk on the image border (else voff)
-    bool f_plain = false;
-    unsigned long long fix = 0;
-    auto fetch_setup = [&]() {
-        const bool any = f_left > 0;
-        const int y0 = 2 * f_ty, x0 = f_cb * G::COLS;
-        const float* xb = x + ((size_t)f_n * Cin + ci0) * HW + ((ptrdiff_t)y0 - 1) * W + (x0 - 4);
-        const float* db = dy + ((size_t)f_n * Cout + co0) * HW + (size_t)y0 * W + x0;
-        rx = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr(xb), 0, clamp_rec(x_end - (const char*)xb), 0x00020000);
-        rd = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr(db), 0, clamp_rec(dy_end - (const char*)db), 0x00020000);
-        const bool first = f_cb == 0, last = f_cb == colBlocks - 1;
-        const bool top = y0 == 0, bot2 = y0 + 1 >= H, bot3 = y0 + 2 >= H;
-        f_plain = any && !first && !last && !top && !bot3;
-        if (f_plain) {                                   // interior chunk: only the channel mask (already in voff)
-            fix = 0;
-        } else {
-            unsigned m = any ? m_ch : 0u;
-            m &= first ? m_first : ~0u;
-            m &= last ? m_last : ~0u;
-            m &= top ? ~m_r0 : ~0u;
-            m &= bot2 ? ~(m_r2 | m_d1) : ~0u;
-            m &= bot3 ? ~m_r3 : ~0u;
-            fix = (any && last) ? fix_last : 0ull;
-            // (a piece whose row or channel is masked needs no fix-up: zeroing zeros is harmless)
+    // the offsets the DMA instructions use: ONE array, rewritten only when a chunk's class differs from the previous chunk's
+    // (interior after interior, or a run along one edge, rewrites nothing)
+    constexpr unsigned G_FIRST = 2, G_LAST = 4, G_TOP = 8, G_BOT = 16, G_NONE = 32;   // (no flag is 1: a bool's zero-extension is selected on the VALU)
+    unsigned eoff[NP];
 #pragma unroll
-            for (int i = 0; i < GNX + GND; ++i) eoff[i] = (m >> i) & 1 ? voff[i] : 0xFFFFFFFFu;
+    for (int i = 0; i < NP; ++i) eoff[i] = voff[i];
+    unsigned e_cls = 0;                                  // the class eoff stands for (0: interior = voff)
+    const unsigned fixable = fe < 4 ? G_LAST : 0u;
+    unsigned fix = 0;                                    // (wave-uniform) nonzero: the chunk just set up has words to fix
+    auto fetch_setup = [&]() __attribute__((always_inline)) {
+        rx = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr((const char*)x + xo), 0, clamp_rec(x_bytes - xo), 0x00020000);
+        rd = __builtin_amdgcn_make_buffer_rsrc(ptmi_uniform_ptr((const char*)dy + dO), 0, clamp_rec(dy_bytes - dO), 0x00020000);
+        // class 0 = interior chunk: every row and column of both patches inside the image -- the loop-invariant offsets serve
+        const unsigned cls = f_left > 0 ? (f_cb == 0 ? G_FIRST : 0u) | (f_cb == colBlocks - 1 ? G_LAST : 0u) |
+                                              (f_ty == 0 ? G_TOP : 0u) | (f_ty == tilesY2 - 1 ? G_BOT : 0u)
+                                        : G_NONE;
+        fix = cls & fixable;
+        if (cls != e_cls) {
+            e_cls = cls;
+            if (cls == 0) {
+#pragma unroll
+                for (int i = 0; i < NP; ++i) eoff[i] = voff[i];
+            } else {
+                const unsigned a = inv_col & ((cls & G_FIRST ? 0xFFFFu : 0u) | (cls & G_LAST ? 0xFFFFu << 16 : 0u));
+                const unsigned b = inv_row & ((cls & G_TOP ? 0xFFFFu : 0u) | (cls & G_BOT ? 0xFFFFu << 16 : 0u));
+                const unsigned inv = a | a >> 16 | b | b >> 16 | (cls & G_NONE ? 0xFFFFu : 0u);
+#pragma unroll
+                for (int i = 0; i < NP; ++i) eoff[i] = voff[i] | (unsigned)((int)(inv << (31 - i)) >> 31);   // out: 0xFFFFFFFF
+            }
         }
         --f_left;
+        long long sx = G::COLS * 4, sd = G::COLS * 4;
         if (++f_cb == colBlocks) {
             f_cb = 0;
-            if (++f_ty == tilesY2) { f_ty = 0; ++f_n; }
+            sx = sd = stepRow;
+            if (++f_ty == tilesY2) { f_ty = 0; sx = stepImgX; sd = stepImgD; }
         }
+        xo += sx;
+        dO += sd;
     };
-    auto fetch_piece = [&](int idx, int stage) {
-        // (a scalar branch instead of a per-lane select: every VALU instruction in the loop costs MFMA time)
+    auto fetch_piece = [&](int idx, int stage) __attribute__((always_inline)) {
         wlds_void_t* dst = (wlds_void_t*)(lds + stage * GSTAGE + (idx < GNX ? GDYR + wave * 256 + idx * WNT * 4 : wave * 256 + (idx - GNX) * WNT * 4));
-        if (f_plain) __builtin_amdgcn_raw_ptr_buffer_load_lds(idx < GNX ? rx : rd, dst, 16, (int)voff[idx], 0, 0, 0);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(idx < GNX ? rx : rd, dst, 16, (int)eoff[idx], 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(idx < GNX ? rx : rd, dst, 16, (int)eoff[idx], 0, 0, 0);
     };
-    auto fixup = [&](int stage, unsigned long long fm) {
-        if ((unsigned)fm | (unsigned)(fm >> 32)) {
+    auto fixup = [&](int stage) __attribute__((always_inline)) {   // of a chunk in the last column block whose edge cuts a piece (fe < 4)
+        float* const st = lds + stage * GSTAGE;
 #pragma unroll
-            for (int i = 0; i < GNX + GND; ++i) {
-                float* pc = lds + stage * GSTAGE + (i < GNX ? GDYR + (tid + i * WNT) * 4 : (tid + (i - GNX) * WNT) * 4);
+        for (int k = 0; k < WGF; ++k) {
+            unsigned pk = fpk[k / 2];
+            asm volatile("" : "+v"(pk));                 // (unpacked here, not hoisted out of the chunk loop into registers of its own)
+            const int o = (k & 1) ? pk >> 16 : pk & 0xFFFFu;
 #pragma unroll
-                for (int e = 1; e < 4; ++e)
-                    if (fm & (1ull << (4 * i + e))) pc[e] = 0.f;
-            }
+            for (int e = 1; e < 4; ++e)
+                if (e >= fe) st[o + e] = 0.f;
         }
     };
 
@@ -821,14 +882,14 @@ __global__ __launch_bounds__(WNT, 1) void conv3x3_wino_wgrad_kernel(
         fetch_setup();
 #pragma unroll
         for (int idx = 0; idx < GNX + GND; ++idx) fetch_piece(idx, 0);
-        const unsigned long long fix0 = fix;
+        const unsigned fix0 = fix;
         fetch_setup();
 #pragma unroll
         for (int idx = 0; idx < 8; ++idx) fetch_piece(idx, 1);
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        fixup(0, fix0);
+        if (fix0) fixup(0);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        unsigned long long fix_h = fix;          // fix-ups of the next chunk to be handed over (chunk 1)
+        unsigned fix_h = fix;                    // whether the next chunk to be handed over (chunk 1) has fix-ups
         {   // operands of k-step 0 (transformed) and raw operands of k-step 1
 #pragma unroll
             for (int P = 0; P < 10; ++P) raw_read(lds, window_base(lds, 0), 0, RA[0], RB[0], P);
@@ -860,7 +921,9 @@ __global__ __launch_bounds__(WNT, 1) void conv3x3_wino_wgrad_kernel(
                     // hand-over: the next chunk's pieces (all issued by k-step 1) have landed; edge fix-ups; barrier; then the
                     // stage this chunk occupied is free (its last raw reads were k-step KSN - 3's) and the fetch of chunk + 2 starts
                     wino_vmwait0();
-                    fixup(cur ^ 1, fix_h);
+                    // Only a chunk in the last column block has words to fix: a wave-uniform property, so every other chunk
+                    // passes with one scalar branch
+                    if (fix_h) fixup(cur ^ 1);
                     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                     fetch_setup();
                     fix_h = fix;

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
     // ---- DMA-side state of a tile: the lane's patch pieces (channel, patch row, 16-B piece) -> byte offset from the chunk's first
     // plane of the tile's first image; periods are multiples of 4, so a piece lies in ONE strip
     unsigned n_pvoff[XPI];                                   // the NEXT tile's (the DMA cursors switch to it when they wrap)
-    int n_fix;
+    unsigned n_fix;                                          // the lane's XPI fix-up pieces, ten bits each (make_next, fixup)
     bool n_edge;
     const char* n_xc;
     unsigned n_xleft;
@@ -193,7 +193,12 @@ __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
         const int n = (u0 / period) / bands;                 // image of the first tile column: the address base
         const int s0 = (u0 > 4 ? u0 - 4 : 0) / period;       // strip / image / band of the patch's first column
         const int n0 = s0 / bands, b0 = s0 - n0 * bands;
-        n_fix = 0;                                           // words 1..3 of piece i (bits 4i+1 .. 4i+3) beyond the image edge
+        // Fix-ups: a piece that an image's right edge cuts (gx = W & ~3, W & 3 != 0) is fetched whole, and its words W & 3 .. 3 (the
+        // next row's first pixels) are zeroed in LDS at the hand-over.  Which words is wave-uniform; which of its XPI pieces are cut
+        // is all that differs per lane, and it holds for every chunk of the tile.  So the tile keeps, per DMA instruction i, the
+        // piece of the stage to fix (bits 10 i .. 10 i + 9): the lane's own piece where it is cut, else a padding piece of the stage
+        // (720 .. 767: zero fill, read by nobody), and the hand-over stores without any per-lane test
+        n_fix = 0;
 #pragma unroll
         for (int i = 0; i < XPI; ++i) {
             const int pidx = tid + i * XNT;
@@ -204,11 +209,12 @@ __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
             while (band >= bands) { band -= bands; ++sn; }
             const int gy = band * XTH - 1 + r;
             n_pvoff[i] = 0xFFFFFFFFu;
+            unsigned fp = XPS / 4 + (lane & 31);
             if (valid && pidx < XPS / 4 && gx >= 0 && sn < N && gy >= 0 && gy < H && gx < W) {
                 n_pvoff[i] = (unsigned)(((sn - n) * Cin + ci) * HW + gy * W + gx) * 4u;
-#pragma unroll
-                for (int e = 1; e < 4; ++e) n_fix |= (gx + e >= W) ? (1 << (4 * i + e)) : 0;
+                fp = gx + 4 > W ? (unsigned)pidx : fp;
             }
+            n_fix |= fp << (10 * i);
         }
         n_edge = false;                                      // some loaded piece may straddle the right edge of an image row
         if (valid && (W & 3)) {
@@ -225,7 +231,7 @@ __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
     };
     // the cursors: patch pieces of chunk pcur / slab pieces of chunk ucur of the tile they are in
     unsigned pvoff[XPI];
-    int fix;
+    unsigned fix;
     bool edge;
     const char* xc;
     unsigned xleft;
@@ -284,17 +290,27 @@ __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
         ++pcur;
     };
     auto advance_u = [&]() __attribute__((always_inline)) { wv += XUS * 4; ++ucur; };
-    int fix_ho;                                              // fix-up mask / edge flag of the patch the NEXT hand-over completes (the
+    static_assert(XPI * 10 <= 32 && XPSP / 4 <= (1 << 10) && XPS / 4 + 32 <= XPSP / 4, "wino4p: a lane's fix-up pieces in one register");
+    unsigned fix_ho;                                         // fix-up pieces / edge flag of the patch the NEXT hand-over completes (the
     bool edge_ho;                                            // one issued during the previous chunk)
-    auto fixup = [&](int stage, int fx, bool ed) __attribute__((always_inline)) {
-        if (ed && fx) {
-            float* pw = ldsP + stage + tid * 4;
+    const int fix_e0 = W & 3;                                // the first word of a cut piece past the edge (an edge implies 1 .. 3)
+    // (ed is wave-uniform, and so are the words: scalar branches around XPI .. 2 XPI unconditional stores -- words 2, 3 in one)
+    auto fixup = [&](int stage, unsigned fx, bool ed) __attribute__((always_inline)) {
+        if (ed) {
+            float* pw = ldsP + stage;
+            auto words = [&](auto e0_c) __attribute__((always_inline)) {
+                constexpr int E0 = decltype(e0_c)::value;
 #pragma unroll
-            for (int i = 0; i < XPI; ++i) {
-#pragma unroll
-                for (int e = 1; e < 4; ++e)
-                    if (fx & (1 << (4 * i + e))) pw[i * XNT * 4 + e] = 0.f;
-            }
+                for (int i = 0; i < XPI; ++i) {
+                    float* pc = pw + ((fx >> (10 * i)) & 0x3FFu) * 4;
+                    if constexpr (E0 == 1) pc[1] = 0.f;
+                    if constexpr (E0 <= 2) *(f32x2*)(pc + 2) = (f32x2){0.f, 0.f};
+                    else pc[3] = 0.f;
+                }
+            };
+            if (fix_e0 == 3) words(std::integral_constant<int, 3>{});
+            else if (fix_e0 == 2) words(std::integral_constant<int, 2>{});
+            else words(std::integral_constant<int, 1>{});
         }
     };
 
@@ -398,10 +414,10 @@ __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
         advance_u();
     };
     issue_patch(0);
-    const int fix_p0 = fix; const bool edge_p0 = edge;
+    const unsigned fix_p0 = fix; const bool edge_p0 = edge;
     issue_u(0);
     issue_patch(XPSP);
-    const int fix_p1 = fix; const bool edge_p1 = edge;
+    const unsigned fix_p1 = fix; const bool edge_p1 = edge;
     issue_u(XUS);
     issue_patch(2 * XPSP);
     fix_ho = fix; edge_ho = edge;
@@ -513,9 +529,9 @@ __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
                 if (!skipwait) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(x_dma_before(XHAND)) : "memory");   // [x4:ho] [x4:hov]
                 skipwait = false;
                 // fix-ups of that patch.  edge_ho is wave-uniform: a scalar branch of its own, so that only a chunk whose patch
-                // straddles an image's right edge pays the per-lane mask test (merged into one exec mask -- what the compiler makes
-                // of `edge_ho && fix_ho`, and the empty asm prevents -- every chunk paid a v_cmp -> s_and_saveexec round trip between
-                // two MFMAs: 1.5 - 2.5 % of the layer, profiles/handover_per_layer.txt)
+                // straddles an image's right edge pays for the fix-up stores (a per-lane test in every chunk cost a v_cmp ->
+                // s_and_saveexec round trip between two MFMAs: 1.5 - 2.5 % of the layer, profiles/handover_per_layer.txt; and such a
+                // chunk itself needs none either: fixup)
                 if (edge_ho) {   // [x4:ho] [x4:hof]
                     asm volatile("" ::: "memory");   // [x4:ho] [x4:hof]
                     fixup(pf, fix_ho, true);   // [x4:ho] [x4:hof]

@@ -227,7 +227,8 @@ _WINO4_WGRAD_MIN_FILL = 0.9    # ... and walks the map in chunks of 4 rows x 16 
                                # F(2x2,3x3)-domain kernel (7- or 8-k-step chunks, whichever fits the row) was faster (50 x 83, fill 0.83:
                                # 0.91x).  Re-measured with the border masks built once (tools/exp/wino4w_bench.py --layers conv5_1
                                # --n 48, twice; profiles/wino4w_border_masks_per_layer.txt): 50 x 83 1.034x / 1.031x (3.82 against
-                               # 3.95 ms; 100 x 166 was 1.08x and 200 x 333 1.17x before it).  So 50 x 83 would now gain 3 % here (0.5 ms of the step);
+                               # 3.95 ms; 100 x 166 was 1.08x and 200 x 333 1.17x before it); with both kernels' chunk hand-over and set-up
+                               # cut since (profiles/edge_fixup_per_layer.txt): 1.08x (3.38 against 3.65 ms).  So 50 x 83 would now gain 8 % here (1 ms of the step);
                                # the bar stays because tests/test_wino_gpu.py pins those maps to the older kernel -- lowering it is a
                                # change of its own together with that test
 
