@@ -195,7 +195,8 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 8 ? 4 : 3)) void conv3x3_buf_
     // per element, issued while the CU's other waves stream MFMAs) holding the workgroup's slot for 30-40 us after
     // its last MFMA -- 5-17 % of its life.  Here every store is `buffer_store_dword`: the per-lane byte offset
     // (pixel, + 4 channels for the upper lane half) is computed once, the channel advance is a scalar offset, and
-    // out-of-image pixels (offset 0xFFFFFFFF) / channels >= Cout (past num_records) are dropped by the range check.
+    // out-of-image pixels (offset 0xFFFFFFFF) / channels >= Cout (past num_records) are dropped by the range check,
+    // which counts the scalar offset too (held under guard bands by tests/test_conv_bounds_gpu.py).
     const int py = y0 + rb + pr;
     const int half4 = 4 * (lane >> 5);
     const int co_w = cot * BM + wm * 64;                                   // wave-uniform first channel

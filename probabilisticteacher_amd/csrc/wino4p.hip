@@ -237,8 +237,8 @@ __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
     unsigned xleft;
     const float* slab;
     int urange;
-    unsigned wv;                                             // byte offset of the lane's piece of slab chunk ucur (the range check covers
-    int pcur, ucur;                                          // voffset only: beyond the slab = zero fill)
+    unsigned wv;                                             // byte offset of the lane's piece of slab chunk ucur, chunk advance included
+    int pcur, ucur;                                          // (the range check is on vector + scalar offset: beyond the slab = zero fill)
     auto patch_wrap = [&]() __attribute__((always_inline)) {
         if (pcur == nChunks) {
 #pragma unroll
