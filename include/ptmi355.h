@@ -377,6 +377,18 @@ int ptmi_iou_match_batched(const float* gt_all, const int32_t* gt_off, const flo
                            int nimg, int64_t max_boxes, int64_t total_gt, const float* thresholds_host,
                            const int* labels_host, int n_thr, int allow_low_quality, int64_t* matched_idx,
                            int8_t* matched_label, float* matched_iou, float* ws, ptmi_stream_t s);
+/* ptmi_iou_match_batched with MODEL.RPN.BOUNDARY_THRESH folded in (rpn.py:421-425 -> D2 0.5 Boxes.inside_box): the same
+ * arguments plus sizes_hw (nimg, 2) float32 DEVICE = (h, w) per image (the layout ptmi_rpn_prepare takes) and
+ * boundary_thresh = t >= 0.  box_off must be NULL (one box set shared by all images; anything else is an argument error).
+ * Box (x1, y1, x2, y2) is inside image i iff x1 >= -t && y1 >= -t && x2 < w_i + t && y2 < h_i + t, compared in fp32 (upper
+ * bounds strict, a NaN coordinate is outside); every box that is not inside gets label -1.  The test sits where the label is
+ * stored, after the thresholds and the low-quality rule, so there is no extra pass over nimg * max_boxes and no extra launch.
+ * matched_idx and matched_iou are bit for bit those of ptmi_iou_match_batched. */
+int ptmi_iou_match_batched_bounds(const float* gt_all, const int32_t* gt_off, const float* boxes, const int32_t* box_off,
+                                  int nimg, int64_t max_boxes, int64_t total_gt, const float* thresholds_host,
+                                  const int* labels_host, int n_thr, int allow_low_quality, int64_t* matched_idx,
+                                  int8_t* matched_label, float* matched_iou, float* ws, const float* sizes_hw,
+                                  float boundary_thresh, ptmi_stream_t s);
 /* D2 subsample_labels (rpn.py:433 via RPN._subsample_labels; D2 StandardROIHeads._sample_proposals) for
  * a batch of label vectors without host syncs: cls_all int64 (concatenated; -1 ignore, bg_label background, anything
  * else foreground), keys_all i.i.d. uniform keys, offsets (nimg+1) int32 DEVICE.  Per image: n_fg = min(#fg,

@@ -103,6 +103,8 @@ SIGNATURES = {
     "ptmi_iou_match": (_i, [_vp, _vp, _i, _i64, ctypes.POINTER(_f), ctypes.POINTER(_i), _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ptmi_iou_match_batched": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i64, ctypes.POINTER(_f), ctypes.POINTER(_i), _i, _i,
                                     _vp, _vp, _vp, _vp, _vp]),
+    "ptmi_iou_match_batched_bounds": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i64, ctypes.POINTER(_f), ctypes.POINTER(_i), _i, _i,
+                                           _vp, _vp, _vp, _vp, _vp, _f, _vp]),
     "ptmi_rpn_subsample_relabel": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp]),
     "ptmi_sample_by_keys": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ptmi_segsort_ws_bytes": (_i64, [_i64, _i]),

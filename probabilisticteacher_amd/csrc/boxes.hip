@@ -267,11 +267,21 @@ __global__ __launch_bounds__(256) void iou_match_pass1(const float* __restrict__
     iou_match_pass1_body(gt, boxes, m, nb, midx, miou, best_bits);
 }
 
+// D2 0.5 Boxes.inside_box((h, w), t) in fp32: strict upper bounds; a NaN coordinate fails its comparison, so the box is outside.
+__device__ __forceinline__ bool box_inside_image(const float4 b, float h, float w, float t)
+{
+    return b.x >= -t && b.y >= -t && b.z < w + t && b.w < h + t;
+}
+
+// BOUNDS (ptmi_iou_match_batched_bounds): a box that is not inside its (bh, bw) image by bt gets label -1 where the label is
+// stored, i.e. after the thresholds and the low-quality rule have had their say (rpn.py:421-425 follows the Matcher).
+template <bool BOUNDS>
 __device__ __forceinline__ void iou_match_pass2_body(const float* __restrict__ gt, const float* __restrict__ boxes,
                                                      int m, int64_t nb, const float* __restrict__ miou,
                                                      const int* __restrict__ best_bits, float t0, float t1, int l0,
                                                      int l1, int l2, int n_thr, int lowq,
-                                                     int8_t* __restrict__ mlabel)
+                                                     int8_t* __restrict__ mlabel, float bh = 0.f, float bw = 0.f,
+                                                     float bt = 0.f)
 {
     __shared__ float4 sg[256];
     __shared__ float sa[256];
@@ -305,6 +315,7 @@ __device__ __forceinline__ void iou_match_pass2_body(const float* __restrict__ g
         }
         if (hit) lab = 1;
     }
+    if (BOUNDS && !box_inside_image(b, bh, bw, bt)) lab = -1;
     if (j < nb) mlabel[j] = (int8_t)lab;
 }
 
@@ -314,7 +325,7 @@ __global__ __launch_bounds__(256) void iou_match_pass2(const float* __restrict__
                                                        int l1, int l2, int n_thr, int lowq,
                                                        int8_t* __restrict__ mlabel)
 {
-    iou_match_pass2_body(gt, boxes, m, nb, miou, best_bits, t0, t1, l0, l1, l2, n_thr, lowq, mlabel);
+    iou_match_pass2_body<false>(gt, boxes, m, nb, miou, best_bits, t0, t1, l0, l1, l2, n_thr, lowq, mlabel);
 }
 
 // Batched over images (blockIdx.y): gt rows gt_off[i] .. gt_off[i+1] against box rows box_off[i] .. box_off[i+1], or
@@ -352,8 +363,50 @@ __global__ __launch_bounds__(256) void iou_match_pass2_batched(const float* __re
     const int64_t b0 = box_off ? box_off[img] : 0, nb = box_off ? box_off[img + 1] - b0 : nb_shared;
     const int64_t o0 = box_off ? b0 : (int64_t)img * nb_shared;
     if ((int64_t)blockIdx.x * 256 >= nb || m == 0) return;
-    iou_match_pass2_body(gt + 4 * (size_t)g0, boxes + 4 * (size_t)b0, m, nb, miou + o0, best_bits + g0, t0, t1, l0, l1, l2,
-                         n_thr, lowq, mlabel + o0);
+    iou_match_pass2_body<false>(gt + 4 * (size_t)g0, boxes + 4 * (size_t)b0, m, nb, miou + o0, best_bits + g0, t0, t1, l0, l1, l2,
+                                n_thr, lowq, mlabel + o0);
+}
+
+// ptmi_iou_match_batched_bounds: the two batched passes over ONE shared box set (box_off == NULL) with the inside-image test
+// folded into the stores of the label -- pass 1 for an image without gt (its only label store), pass 2 for every other image.
+// sizes_hw (nimg, 2) = (h, w) per image.  matched_idx / matched_iou are written exactly as by the kernels above.
+__global__ __launch_bounds__(256) void iou_match_pass1_batched_bounds(const float* __restrict__ gt, const int32_t* __restrict__ gt_off,
+                                                                      const float* __restrict__ boxes, int64_t nb,
+                                                                      int64_t* __restrict__ midx, float* __restrict__ miou,
+                                                                      int8_t* __restrict__ mlabel, int* __restrict__ best_bits,
+                                                                      int label_nomatch, const float* __restrict__ sizes_hw,
+                                                                      float bt)
+{
+    const int img = blockIdx.y;
+    const int g0 = gt_off[img], m = gt_off[img + 1] - g0;
+    const int64_t o0 = (int64_t)img * nb;
+    if ((int64_t)blockIdx.x * 256 >= nb) return;
+    if (m == 0) {
+        const int64_t j = blockIdx.x * 256ll + threadIdx.x;
+        if (j < nb) {
+            const bool in = box_inside_image(reinterpret_cast<const float4*>(boxes)[j], sizes_hw[2 * img], sizes_hw[2 * img + 1], bt);
+            midx[o0 + j] = 0;
+            miou[o0 + j] = 0.f;
+            mlabel[o0 + j] = (int8_t)(in ? label_nomatch : -1);
+        }
+        return;
+    }
+    iou_match_pass1_body(gt + 4 * (size_t)g0, boxes, m, nb, midx + o0, miou + o0, best_bits + g0);
+}
+
+__global__ __launch_bounds__(256) void iou_match_pass2_batched_bounds(const float* __restrict__ gt, const int32_t* __restrict__ gt_off,
+                                                                      const float* __restrict__ boxes, int64_t nb,
+                                                                      const float* __restrict__ miou, const int* __restrict__ best_bits,
+                                                                      float t0, float t1, int l0, int l1, int l2, int n_thr, int lowq,
+                                                                      int8_t* __restrict__ mlabel, const float* __restrict__ sizes_hw,
+                                                                      float bt)
+{
+    const int img = blockIdx.y;
+    const int g0 = gt_off[img], m = gt_off[img + 1] - g0;
+    const int64_t o0 = (int64_t)img * nb;
+    if ((int64_t)blockIdx.x * 256 >= nb || m == 0) return;
+    iou_match_pass2_body<true>(gt + 4 * (size_t)g0, boxes, m, nb, miou + o0, best_bits + g0, t0, t1, l0, l1, l2, n_thr, lowq,
+                               mlabel + o0, sizes_hw[2 * img], sizes_hw[2 * img + 1], bt);
 }
 
 // D2 subsample_labels for a batch of label vectors without host round trips.  Element j of image i
@@ -858,6 +911,37 @@ int ptmi_iou_match_batched(const float* gt_all, const int32_t* gt_off, const flo
                        matched_iou, reinterpret_cast<const int*>(ws), t0, t1, labels_host[0], labels_host[1],
                        n_thr == 2 ? labels_host[2] : 0, n_thr, allow_low_quality, matched_label);
     PTMI_LAUNCH_CHECK("iou_match_pass2_batched");
+    return 0;
+}
+
+int ptmi_iou_match_batched_bounds(const float* gt_all, const int32_t* gt_off, const float* boxes, const int32_t* box_off,
+                                  int nimg, int64_t max_boxes, int64_t total_gt, const float* thresholds_host,
+                                  const int* labels_host, int n_thr, int allow_low_quality, int64_t* matched_idx,
+                                  int8_t* matched_label, float* matched_iou, float* ws, const float* sizes_hw,
+                                  float boundary_thresh, ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(gt_off && boxes && thresholds_host && labels_host && matched_idx && matched_label && matched_iou &&
+                       nimg > 0 && max_boxes >= 0 && total_gt >= 0,
+                   "iou_match_batched_bounds: bad args");
+    PTMI_CHECK_ARG(!box_off, "iou_match_batched_bounds: one box set shared by all images only (box_off must be NULL)");
+    PTMI_CHECK_ARG(sizes_hw && boundary_thresh >= 0.f, "iou_match_batched_bounds: sizes_hw missing or boundary_thresh < 0");
+    PTMI_CHECK_ARG(n_thr == 1 || n_thr == 2, "iou_match_batched_bounds: n_thr must be 1 or 2");
+    PTMI_CHECK_ARG(total_gt == 0 || (gt_all && ws), "iou_match_batched_bounds: gt/ws missing");
+    if (max_boxes == 0) return 0;
+    hipStream_t st = (hipStream_t)s;
+    if (total_gt > 0) {
+        hipError_t e = hipMemsetAsync(ws, 0, sizeof(float) * (size_t)total_gt, st);   // bits of +0.0f
+        if (e != hipSuccess) { ptmi_set_error("iou_match_batched_bounds: memset failed"); return -2; }
+    }
+    const dim3 grid((unsigned)((max_boxes + 255) / 256), (unsigned)nimg);
+    hipLaunchKernelGGL(iou_match_pass1_batched_bounds, grid, dim3(256), 0, st, gt_all, gt_off, boxes, max_boxes, matched_idx,
+                       matched_iou, matched_label, reinterpret_cast<int*>(ws), labels_host[0], sizes_hw, boundary_thresh);
+    PTMI_LAUNCH_CHECK("iou_match_pass1_batched_bounds");
+    const float t0 = thresholds_host[0], t1 = n_thr == 2 ? thresholds_host[1] : 0.f;
+    hipLaunchKernelGGL(iou_match_pass2_batched_bounds, grid, dim3(256), 0, st, gt_all, gt_off, boxes, max_boxes, matched_iou,
+                       reinterpret_cast<const int*>(ws), t0, t1, labels_host[0], labels_host[1],
+                       n_thr == 2 ? labels_host[2] : 0, n_thr, allow_low_quality, matched_label, sizes_hw, boundary_thresh);
+    PTMI_LAUNCH_CHECK("iou_match_pass2_batched_bounds");
     return 0;
 }
 

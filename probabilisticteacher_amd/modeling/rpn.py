@@ -127,7 +127,7 @@ class GuassianRPN(nn.Module):
         self.post_nms_topk = {True: R.POST_NMS_TOPK_TRAIN, False: R.POST_NMS_TOPK_TEST}
         self.nms_thresh = R.NMS_THRESH
         self.min_box_size = float(cfg.MODEL.PROPOSAL_GENERATOR.MIN_SIZE)
-        self.anchor_boundary_thresh = R.BOUNDARY_THRESH
+        self.anchor_boundary_thresh = ops.check_boundary_thresh(R.BOUNDARY_THRESH)     # rpn.py:421-425; negative = off
         self.loss_weight = {"loss_rpn_cls": R.LOSS_WEIGHT, "loss_rpn_loc": R.BBOX_REG_LOSS_WEIGHT * R.LOSS_WEIGHT}
         self.nll_loss, self.kl_loss = uncertainty_losses(cfg.UNSUPNET.MODEL_TYPE)     # box_regression.py:177-183, rpn.py:319-344
 
@@ -193,6 +193,21 @@ class GuassianRPN(nn.Module):
                                       self.pre_nms_topk[self.training], self.post_nms_topk[self.training],
                                       self.min_box_size, self.training)
 
+    def _match_anchors(self, boxes_all, counts, anc, instances):
+        """pairwise_iou + Matcher of every image's boxes against the shared anchors (rpn.py:414-415) and, with
+        MODEL.RPN.BOUNDARY_THRESH >= 0, label -1 for the anchors that are not inside their image (rpn.py:421-425).  An image's
+        size is the one its instances carry, not the padded canvas; the inside test is made anew at every call (the anchor
+        table can be learnable).  On the device both come out of the matcher's own launches; off, the call is the one it was."""
+        t = self.anchor_boundary_thresh
+        if t < 0:
+            return ops.iou_match_batched(boxes_all, counts, anc, None, self.iou_thresholds, self.iou_labels, True)
+        sizes = [inst.image_size for inst in instances]
+        if anc.is_cuda:
+            return ops.iou_match_batched(boxes_all, counts, anc, None, self.iou_thresholds, self.iou_labels, True, sizes, t)
+        midx, lab, iou, gt_off, box_off = ops.iou_match_batched(boxes_all, counts, anc, None, self.iou_thresholds,
+                                                                self.iou_labels, True)
+        return midx, sampling.boundary_relabel(lab, anc, sizes, t), iou, gt_off, box_off
+
     # ------------------------------------------------------------------ supervised (rpn.py:191-255, 363-448)
     def _losses_sup(self, anchors, logits, d8, gt_instances):
         n, r = logits.shape
@@ -201,8 +216,7 @@ class GuassianRPN(nn.Module):
             # whole batch: one IoU-match launch pair, one sync-free relabel, one nonzero
             counts = [len(inst.gt_boxes) for inst in gt_instances]
             gt_all = torch.cat([inst.gt_boxes.tensor for inst in gt_instances], 0)
-            midx, lab_all, _, gt_off, _ = ops.iou_match_batched(gt_all, counts, anc, None, self.iou_thresholds,
-                                                                self.iou_labels, True)
+            midx, lab_all, _, gt_off, _ = self._match_anchors(gt_all, counts, anc, gt_instances)
             lab_all = sampling.keyed_relabel(lab_all, self.batch_size_per_image, self.positive_fraction, 0)
             if self.statistics is not None:                 # rpn.py:222-228, as device counts (no .item())
                 self.statistics.put_rpn_labels(ops.label_counts(lab_all), n, lab_all.numel())
@@ -229,8 +243,7 @@ class GuassianRPN(nn.Module):
             # positives of image i select rows of the concatenated pseudo-label tensors through per-image offsets
             counts = [len(inst.pseudo_boxes) for inst in pseudo]
             pb_all = torch.cat([inst.pseudo_boxes.tensor for inst in pseudo], 0)
-            midx, lab_all, _, gt_off, _ = ops.iou_match_batched(pb_all, counts, anc, None, self.iou_thresholds,
-                                                                self.iou_labels, True)
+            midx, lab_all, _, gt_off, _ = self._match_anchors(pb_all, counts, anc, pseudo)
             flat = torch.nonzero(lab_all.view(-1) == 1).squeeze(1)                 # positives only, no subsampling
             img = torch.div(flat, r, rounding_mode="floor")
             sel = midx.view(-1)[flat] + gt_off[img].long()

@@ -95,6 +95,20 @@ def keyed_topk(mask: torch.Tensor, keys: torch.Tensor, k: int):
     return idx, vals < NOT_A_CANDIDATE
 
 
+def boundary_relabel(labels: torch.Tensor, anchors: torch.Tensor, image_sizes, boundary_thresh: int) -> torch.Tensor:
+    """rpn.py:421-425 for a whole batch: labels (N, R) int8 from the Matcher over ONE anchor set (R, 4); every anchor that is
+    not inside image i = image_sizes[i] (h, w) by `boundary_thresh` pixels (D2 Boxes.inside_box) gets label -1 in row i.
+    boundary_thresh < 0: the labels as they are.  This is the torch statement the CPU tests pin; on the device the product
+    takes the same labels straight from the matcher (ops.iou_match_batched with boundary_thresh, no extra pass or launch)."""
+    if boundary_thresh < 0:
+        return labels
+    from ..structures import Boxes
+    assert labels.dim() == 2 and labels.shape[0] == len(image_sizes) and labels.shape[1] == anchors.shape[0]
+    boxes = Boxes(anchors.detach())
+    inside = torch.stack([boxes.inside_box(size, boundary_thresh) for size in image_sizes])
+    return torch.where(inside, labels, labels.new_full((), -1))
+
+
 def keyed_relabel(labels: torch.Tensor, num_samples: int, positive_fraction: float, bg_label: int) -> torch.Tensor:
     """RPN._subsample_labels (D2) for a whole batch: labels (N, R) int8 in {-1, bg, fg...} ->
     new labels with the sampled positives = 1, sampled negatives = 0, everything else -1.  No host sync."""

@@ -1082,11 +1082,30 @@ def dev_i32(values, device) -> torch.Tensor:
     return torch.tensor(values, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
 
 
+def dev_sizes_hw(image_sizes, device) -> torch.Tensor:
+    """Per-image (h, w) -> (N, 2) float32 device tensor (the layout ptmi_rpn_prepare and ptmi_iou_match_batched_bounds take)
+    without a stream synchronisation (pinned staging, async copy)."""
+    return torch.tensor([[float(h), float(w)] for h, w in image_sizes], dtype=F32).reshape(-1, 2).pin_memory().to(
+        device, non_blocking=True)
+
+
+def check_boundary_thresh(value) -> int:
+    """MODEL.RPN.BOUNDARY_THRESH is an integer, as in D2 (Boxes.inside_box(box_size, boundary_threshold: int)); any negative
+    value means off."""
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise TypeError(f"MODEL.RPN.BOUNDARY_THRESH must be an integer (negative = off), got {value!r}")
+    return value
+
+
 def iou_match_batched(gt_all: torch.Tensor, gt_counts: Sequence[int], boxes: torch.Tensor, box_counts, thresholds,
-                      labels, allow_low_quality: bool):
+                      labels, allow_low_quality: bool, image_sizes_hw=None, boundary_thresh: int = -1):
     """ptmi_iou_match for a whole batch in one launch per pass.  gt_all: the images' gt boxes concatenated
     (gt_counts[i] rows each).  boxes: concatenated per image (box_counts[i] rows each) or, with box_counts=None, ONE
-    box set shared by all images (outputs (N, nb)).  Returns (matched_idx within the image, label int8, iou)."""
+    box set shared by all images (outputs (N, nb)).  Returns (matched_idx within the image, label int8, iou).
+    boundary_thresh >= 0 (MODEL.RPN.BOUNDARY_THRESH, shared box set only): boxes that are not inside their image by that many
+    pixels get label -1 (ptmi_iou_match_batched_bounds); image_sizes_hw = the images' (h, w), a host sequence or an (N, 2)
+    float32 device tensor.  boundary_thresh < 0: the existing entry, image_sizes_hw is not looked at."""
+    boundary_thresh = check_boundary_thresh(boundary_thresh)
     boxes = _chk(boxes.contiguous())
     gt_all = _chk(gt_all.contiguous())
     dev = boxes.device
@@ -1108,7 +1127,18 @@ def iou_match_batched(gt_all: torch.Tensor, gt_counts: Sequence[int], boxes: tor
     ws = _ws("ioumb", max(goff[-1], 1) * 4, dev)
     thr = (ctypes.c_float * len(thresholds))(*[float(t) for t in thresholds])
     lab = (ctypes.c_int * len(labels))(*[int(l) for l in labels])
-    if midx.numel():
+    if boundary_thresh >= 0:
+        if box_counts is not None or image_sizes_hw is None:
+            raise _lib.PtmiError("iou_match_batched: boundary_thresh >= 0 needs one shared box set (box_counts=None) and image_sizes_hw")
+        sizes = image_sizes_hw if isinstance(image_sizes_hw, torch.Tensor) else dev_sizes_hw(image_sizes_hw, dev)
+        sizes = _chk(sizes.contiguous())
+        if tuple(sizes.shape) != (n, 2):
+            raise _lib.PtmiError(f"iou_match_batched: image_sizes_hw {tuple(sizes.shape)} for {n} images")
+        if midx.numel():
+            _lib.call("ptmi_iou_match_batched_bounds", _ptr(gt_all), _ptr(gt_off), _ptr(boxes), None, n, nb, goff[-1], thr,
+                      lab, len(thresholds), int(allow_low_quality), _ptr(midx), _ptr(mlab), _ptr(miou), _ptr(ws), _ptr(sizes),
+                      float(boundary_thresh), _stream())
+    elif midx.numel():
         _lib.call("ptmi_iou_match_batched", _ptr(gt_all), _ptr(gt_off), _ptr(boxes), _ptr(box_off), n, nb, goff[-1], thr,
                   lab, len(thresholds), int(allow_low_quality), _ptr(midx), _ptr(mlab), _ptr(miou), _ptr(ws), _stream())
     return midx, mlab, miou, gt_off, box_off

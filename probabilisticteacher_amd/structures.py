@@ -41,6 +41,15 @@ class Boxes:
         t = self.tensor
         return ((t[:, 2] - t[:, 0]) > threshold) & ((t[:, 3] - t[:, 1]) > threshold)
 
+    def inside_box(self, box_size: Tuple[int, int], boundary_threshold: int = 0) -> torch.Tensor:
+        """D2 0.5 Boxes.inside_box: bool (N,), True where the box lies inside the (h, w) image grown by the threshold on every
+        side.  The upper bounds are strict; a NaN coordinate is outside.  Host logic and CPU tests; the RPN labels on the device
+        get the same test from ptmi_iou_match_batched_bounds."""
+        h, w = box_size
+        t = self.tensor
+        return ((t[..., 0] >= -boundary_threshold) & (t[..., 1] >= -boundary_threshold)
+                & (t[..., 2] < w + boundary_threshold) & (t[..., 3] < h + boundary_threshold))
+
     def scale(self, scale_x: float, scale_y: float) -> None:
         self.tensor = self.tensor * self.tensor.new_tensor([scale_x, scale_y, scale_x, scale_y])
 
