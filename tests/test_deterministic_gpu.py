@@ -130,6 +130,39 @@ def test_roi_pool_backward_det(inputs):
     close(fa.grad.cpu().numpy(), want, 1e-4, 1e-4, "roi_pool bwd atomic")
 
 
+@pytest.mark.parametrize("fh,fw", [(64, 128), (100, 120)])
+def test_roi_pool_backward_det_at_the_lds_tile_limit(fh, fw):
+    """the kernel holds a plane in LDS tiles of 8192 cells: a plane of exactly one tile (64 x 128) and one of two tiles, the second
+    partial (100 x 120 = 12000 cells); images with 0, 3 and 21 ROIs, the edge boxes of tests/roi_pooler_ref.py"""
+    from probabilisticteacher_amd import ops
+    counts, c = (0, 3, 21), 3
+    rois_np, offs_np = ref.counts_to_rois(ref.box_set(sum(counts), fh, fw, 1 / 16, 9), counts)
+    gen = torch.Generator().manual_seed(fh + fw)
+    feat = torch.randn(len(counts), c, fh, fw, generator=gen)
+    gy = torch.randn(len(rois_np), c, 7, 7, generator=gen)
+    _, arg = ref.roi_pool(feat.numpy(), rois_np, 7, 1 / 16)
+    assert (arg >= 8192).any() == (fh * fw > 8192) and (arg == fh * fw - 1).any() and (arg == -1).any()
+    want = ref.roi_pool_backward(gy.numpy(), arg, rois_np, feat.shape)
+    gd, rd, offs = gy.to(DEV), torch.from_numpy(rois_np).to(DEV), torch.from_numpy(offs_np).to(DEV)
+    grads = []
+    for _ in range(2):
+        fd = feat.to(DEV).requires_grad_()
+        with ops.deterministic(True):
+            ops.roi_pool(fd, rd, 7, 1 / 16, img_offsets=offs).backward(gd)
+        grads.append(fd.grad)
+    assert torch.equal(grads[0], grads[1]), "deterministic ROIPool backward: two runs, the same bits"
+    close(grads[0].cpu().numpy(), want, 1e-4, 1e-4, f"roi_pool bwd det {fh}x{fw}")
+    assert not grads[0][0].any(), "an image without ROIs gets an exactly zero gradient"
+    perm = torch.randperm(len(rois_np), generator=torch.Generator().manual_seed(6)).to(DEV)
+    fd = feat.to(DEV).requires_grad_()
+    with ops.deterministic(True):
+        ops.roi_pool(fd, rd[perm], 7, 1 / 16).backward(gd[perm])
+    close(fd.grad.cpu().numpy(), want, 1e-4, 1e-4, "roi_pool bwd det, ungrouped rows")
+    fa = feat.to(DEV).requires_grad_()
+    ops.roi_pool(fa, rd, 7, 1 / 16).backward(gd)
+    close(fa.grad.cpu().numpy(), want, 1e-4, 1e-4, "roi_pool bwd atomic")
+
+
 @pytest.mark.parametrize("rows,n_dst", [(6000, 9), (4096, 9), (700, 150)])
 def test_get_deltas_source_gradient_det(rows, n_dst):
     """thousands of rows onto 9 anchors (one destination tile, two row chunks), and more destinations than one tile holds"""

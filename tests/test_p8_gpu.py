@@ -392,20 +392,25 @@ def test_p8_conv3_2_at_n48_bench_launch_shape_vs_torch():
     assert float((db.cpu() - br.grad).abs().max()) <= 1e-4 * sb, "conv3_2 bias grad n=48"
 
 
-@pytest.mark.parametrize("n,c,h,w,per", [(2, 16, 25, 31, 19), (3, 64, 50, 83, 171), (1, 8, 12, 9, 8)])
+@pytest.mark.parametrize("n,c,h,w,per", [(2, 16, 25, 31, 19), (3, 64, 50, 83, 171), (1, 8, 12, 9, 8),
+                                         (4, 8, 12, 9, (0, 3, 0, 21)), (3, 8, 12, 9, (5, 14, 0))])
 def test_roi_align_writing_the_linear_layers_bf16_operands_equals_pool_then_pack(n, c, h, w, per):
     """SOLVER.AMP.ENABLED box head: ROIAlign -> flatten -> Linear + ReLU as one node whose ROIAlign kernel writes the GEMM's bf16
     operands (xk, and xt for the weight gradient) itself == the fp32 ROIAlign followed by p8.linear's operand packs: the same bf16
-    values, hence y, dW, db and the feature-map gradient bit for bit (ROI counts that are not multiples of 8: the zero tail of xt)"""
+    values, hence y, dW, db and the feature-map gradient bit for bit (ROI counts that are not multiples of 8: the zero tail of xt).
+    `per`: ROIs per image, or the per-image counts -- (0, 3, 0, 21): images without ROIs first and in the middle, R = 24 a multiple
+    of 8, one ROI more than the kernel's 20 slots; (5, 14, 0): R = 19, the zeroed tail octet of xt next to an empty last image"""
     from probabilisticteacher_amd import ops, p8
     gen = g(n * 1000 + c)
     feat = torch.randn(n, c, h, w, generator=gen)
-    r = n * per
+    counts = torch.tensor([per] * n if isinstance(per, int) else list(per))
+    assert len(counts) == n
+    r = int(counts.sum())
     ctr = torch.rand(r, 2, generator=gen) * torch.tensor([w * 16.0, h * 16.0])
     wh = 24 + torch.rand(r, 2, generator=gen) * 200
-    img = torch.arange(n).repeat_interleave(per).float()
+    img = torch.arange(n).repeat_interleave(counts).float()
     rois = torch.cat([img[:, None], ctr - wh / 2, ctr + wh / 2], 1).to(DEV)
-    offs = torch.arange(0, (n + 1) * per, per, dtype=torch.int32, device=DEV)
+    offs = torch.cat([torch.zeros(1, dtype=torch.int64), counts.cumsum(0)]).to(torch.int32).to(DEV)
     k, nout = c * 49, 40
     wt = (torch.randn(nout, k, generator=gen) * 0.05).to(DEV)
     b = (torch.randn(nout, generator=gen) * 0.1).to(DEV)
