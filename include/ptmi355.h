@@ -632,6 +632,24 @@ int ptmi_clip_sgd_step_seg(float* p, const float* g, float* buf, int64_t n, cons
                            float clip_value, const float* seg_norm, float lr, float momentum, float weight_decay,
                            int first, ptmi_stream_t s);
 
+/* ------------------------------------------------------------------ anomaly mode (csrc/anomaly.hip)
+ * PTrainer(detect_anomaly=True); the reference runs every step under torch.autograd.set_detect_anomaly (trainer.py:167).
+ * Does a tensor hold a NaN or an infinity, and where is the first: x = n elements of dtype 0 (fp32) or 1 (bf16, 2-byte elements
+ * as P8 tensors hold them), classified on the bit pattern (exponent all ones; mantissa zero or not).
+ *   flags[slot] |= 1 if any element is NaN, |= 2 if any is +-inf;  first[slot] = min(first[slot], lowest non-finite index).
+ * The caller resets the slots (flags 0, first INT64_MAX); scans into one slot accumulate.  One read pass; a clean tensor causes
+ * NO global write (flags are combined inside the wave and the block, one lane of a block that found something issues the
+ * atomicOr / atomicMin), and the index is the lowest one whatever the grid or the timing.  n == 0: nothing is launched, 0.
+ * slot outside [0, nslots), a null pointer with n > 0 or an unknown dtype: < 0, ptmi_last_error() = "nonfinite_scan: ...". */
+int ptmi_nonfinite_scan(const void* x, int64_t n, int dtype, int32_t* flags, int64_t* first, int slot, int nslots,
+                        ptmi_stream_t s);
+/* The same two flag bits for every SEGMENT of the flat gradient buffer g, over the tables of the per-parameter clipping kernels
+ * above (seg_off int64[S + 1], chunks int64[C][2]; one workgroup per chunk, a descriptor outside its segment is skipped).
+ * seg_flags int32[S] is cleared on the stream first; g is not written.  n == 0 or S == 0: nothing is launched, 0 is returned
+ * (also with null tables). */
+int ptmi_seg_nonfinite(const float* g, int64_t n, const int64_t* seg_off, int S, const int64_t* chunks, int C,
+                       int32_t* seg_flags, ptmi_stream_t s);
+
 /* ------------------------------------------------------------------ image prep (N18)
  * rcnn.py:40 -> D2 preprocess_image: out[i] (3,hmax,wmax) = (u8 - mean)/std, zero padded.
  * One launch per image (images have individual sizes). */

@@ -4,7 +4,8 @@
 without thresholding, shrink-and-paste `resize`, supervised + unsupervised student forwards, one backward,
 gradient clipping, SGD -- but every heavy piece is a HIP kernel and the per-tensor Python loops of the reference
 (EMA, clip, SGD, metrics `.item()`s) are single launches over flat buffers.  What the reference does only to burn
-time (anomaly mode, empty_cache, gc.collect, a third unused model copy) is not replicated."""
+time (empty_cache, gc.collect, a third unused model copy) is not replicated; its anomaly mode
+(trainer.py:167) is opt-in: PTrainer(cfg, detect_anomaly=True), probabilisticteacher_amd/anomaly.py."""
 import random
 import time
 from typing import Callable, Dict, List, Optional
@@ -13,6 +14,7 @@ import torch
 import torch.distributed as dist
 
 from .. import ops, seeding
+from ..anomaly import AnomalyError, AnomalySink, flagged_parameters
 from ..modeling import EnsembleTSModel, build_model, sampling
 from ..modeling import statistics as step_statistics
 from ..structures import Boxes, FreeInstances
@@ -28,7 +30,7 @@ class PTrainer:
 
     def __init__(self, cfg, data_loader=None, ratio_fn: Optional[Callable[[], float]] = None,
                  force_grad_reducer: bool = False, grad_reduce: str = "all_reduce", deterministic: Optional[bool] = None,
-                 statistics: bool = False):
+                 statistics: bool = False, detect_anomaly: bool = False):
         """force_grad_reducer: run the bucketed gradient all-reduce (hooks + collectives) even with one rank -- needs an
         initialised process group; the sum over one rank is the identity (single-GPU validation of the DDP path).
         grad_reduce: "all_reduce" or "reduce_scatter" (engine/flat.py: BucketedGradReducer).
@@ -36,7 +38,12 @@ class PTrainer:
         one weight-gradient wave, so that same binary + same GPU model + same world size give the same bits; None = cfg.SEED >= 0.
         statistics: also log what the reference logs beside its losses -- `rpn/num_{pos,neg}_anchors`, `roi_head/num_target_{fg,bg}_
         samples_<branch>`, `fast_rcnn/{cls_accuracy,fg_cls_accuracy,false_negative}` (modeling/statistics.py) -- into `last_metrics`:
-        two counting kernels in the supervised branch, no further device->host read.  Off: the step launches what it launched before."""
+        two counting kernels in the supervised branch, no further device->host read.  Off: the step launches what it launched before.
+        detect_anomaly: the reference's torch.autograd.set_detect_anomaly (trainer.py:167) -- every tensor the autograd functions of
+        ops.py / p8.py produce in forward and backward and every parameter's gradient are checked for NaN / infinity on the device
+        (probabilisticteacher_amd/anomaly.py), and a step that produced one raises AnomalyError BEFORE the update: parameters,
+        momentum and `iter` stay what they were.  Costs one extra read of every activation and gradient and one host read per
+        step.  Off: the step launches what it launched before and allocates nothing."""
         self.cfg = cfg
         self.deterministic = cfg.SEED >= 0 if deterministic is None else bool(deterministic)
         check_optimizer_options(cfg)
@@ -79,6 +86,14 @@ class PTrainer:
         ops.set_tile_schedule("dynamic" if shares_cus else "static")
         ops.set_wgrad_waves(self.ddp_wgrad_waves(bool(cfg.SOLVER.AMP.ENABLED)) if shares_cus else 1)
         ops.set_p8_conv_waves(16 if shares_cus else 1)       # (SOLVER.AMP.ENABLED: the bf16-storage convolution, persistent too)
+        # anomaly mode: the sink of the scan slots, and the segment tables of the per-parameter gradient flags (those of
+        # SOLVER.CLIP_GRADIENTS when it is enabled)
+        self._anomaly, self._anomaly_segments = None, None
+        if detect_anomaly:
+            self._anomaly_segments = (self._segments if self._segments is not None else
+                                      ops.SegmentTable(segment_offsets(self.student), self.student.flat.device))
+            self._anomaly = AnomalySink(self.student.flat.device, segments=self._anomaly_segments.S)
+            self._anomaly_names = [n for n, p in self.student.params.items() if p.requires_grad]     # segment order
         self._first_step = True
         self.joint_student_pass = True      # one backbone pass for the two student branches when they share a canvas
         self.ensem_ts_model = EnsembleTSModel(self.model_teacher, self.model)
@@ -204,7 +219,7 @@ class PTrainer:
     # ------------------------------------------------------------------ the step (trainer.py:263-392)
     def run_step(self, data=None) -> Dict[str, float]:
         with ops.operand_rounding(self.operand_rounding), ops.deterministic(self.deterministic), \
-                sampling.key_generator(self._key_gen):
+                sampling.key_generator(self._key_gen), ops.anomaly(self._anomaly):
             return self._run_step(data)
 
     def _run_step(self, data=None) -> Dict[str, float]:
@@ -214,11 +229,57 @@ class PTrainer:
             data = next(self._data_iter)
         label_data_q, label_data_k, unlabel_data_q, unlabel_data_k = [list(d) for d in data]
         data_time = time.perf_counter() - start
-        U = self.cfg.UNSUPNET
         self.student.zero_grad()
         if self._statistics is not None:
             self._statistics.reset()
+        if self._anomaly is None:
+            record_dict, losses = self._forward(label_data_q, label_data_k, unlabel_data_q, unlabel_data_k)
+        else:
+            self._anomaly.begin_step()
+            try:
+                record_dict, losses = self._forward(label_data_q, label_data_k, unlabel_data_q, unlabel_data_k)
+            except AnomalyError:
+                raise
+            except FloatingPointError as e:
+                # a check inside forward (find_top_rpn_proposals' non-finite proposals) fired first: same error type as a scan
+                # hit, with what the scans saw up to there.  (One rank alone raising in forward leaves the others waiting in
+                # their collectives, with or without this mode -- not changed here.)
+                raise AnomalyError(self.iter, self._anomaly.collect(), (), (), f"raised in forward: {e}") from e
+        losses.backward()
+        self.reducer.finish()                  # DDP gradient average (buckets were launched during backward)
+        if self._anomaly is not None:
+            self._check_anomaly()              # raises BEFORE the update
+        ss = self._clip_and_step(10.0)
+        if self._statistics is not None:
+            record_dict[step_statistics.KEY] = self._statistics
+        self._write_metrics(record_dict, data_time, ss)
+        self.iter += 1
+        return self.last_metrics
 
+    def _check_anomaly(self) -> None:
+        """anomaly mode, after backward and the gradient exchange: one launch flags the parameters whose gradient is non-finite,
+        one device->host copy brings those flags and the scan slots' back; any hit raises AnomalyError.  Several ranks: one
+        all_reduce(MAX) of a per-rank vector, so that every rank raises in the same step and knows which ranks reported."""
+        sink = self._anomaly
+        ops.seg_nonfinite(self.student.grad, self._anomaly_segments, sink.seg_flags)
+        records = sink.collect()
+        params = flagged_parameters(sink.segment_flags, self._anomaly_names, [n for n, _ in self.model.named_parameters()])
+        ranks = []
+        if self.world_size > 1:
+            mine = torch.zeros(self.world_size, dtype=torch.int32, device=self.student.flat.device)
+            mine[dist.get_rank()] = (1 if records else 0) | (2 if params else 0)
+            dist.all_reduce(mine, op=dist.ReduceOp.MAX)
+            seen = mine.cpu().tolist()
+            ranks = [r for r, v in enumerate(seen) if v & 1]
+            hit = any(seen)
+        else:
+            hit = bool(records or params)
+        if hit:
+            raise AnomalyError(self.iter, records, params, ranks)
+
+    def _forward(self, label_data_q, label_data_k, unlabel_data_q, unlabel_data_k):
+        """the forward half of the step (trainer.py:289-381) -> (record_dict, total loss)"""
+        U = self.cfg.UNSUPNET
         if self.iter < U.BURN_UP_STEP:
             batch = self.resize(label_data_q + label_data_k)
             record_dict, _, _, _ = self.model(batch, branch="supervised")
@@ -255,15 +316,7 @@ class PTrainer:
                     losses = losses + v * U.TARGET_UNSUP_LOSS_WEIGHT
                 else:
                     raise NotImplementedError
-
-        losses.backward()
-        self.reducer.finish()                  # DDP gradient average (buckets were launched during backward)
-        ss = self._clip_and_step(10.0)
-        if self._statistics is not None:
-            record_dict[step_statistics.KEY] = self._statistics
-        self._write_metrics(record_dict, data_time, ss)
-        self.iter += 1
-        return self.last_metrics
+        return record_dict, losses
 
     # every loss key a step can produce (burn-in: bare names; mutual learning: _sup / _unsup), in a fixed order, so that
     # ranks exchange equally laid-out vectors whatever subset each of them holds
@@ -310,7 +363,8 @@ class PTrainer:
         m["total_loss"] = sum(v for k, v in m.items() if k[:4] == "loss")
         # the fused ReLU (v_max_f32) turns a NaN pre-activation into 0 where torch.relu propagates it, so a diverged backbone
         # can hide from the loss values; the gradient norm (read back here anyway) is the cheap place where it still shows.
-        # The reference runs under torch.autograd.set_detect_anomaly (trainer.py:266) and raises out of backward().
+        # The reference runs under torch.autograd.set_detect_anomaly (trainer.py:266) and raises out of backward();
+        # PTrainer(detect_anomaly=True) raises before the update and says where.  This late check is what is left without it.
         if gsq != gsq or gsq in (float("inf"), float("-inf")):
             raise FloatingPointError(f"non-finite gradient norm at iteration {self.iter} (losses {m})")
         m["grad_norm"] = gsq ** 0.5

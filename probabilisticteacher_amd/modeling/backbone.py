@@ -59,7 +59,8 @@ class VGGBlock(nn.Module):
             c = getattr(self, f"conv{i + 1}")
             if fuse_pool and i == self.num_convs - 1:
                 return ops.conv3x3_relu_pool_nograd(x, c.weight, c.bias)
-            x = ops.conv3x3(x, c.weight, c.bias, True)
+            with ops.anomaly_scope(f"conv{i + 1}"):
+                x = ops.conv3x3(x, c.weight, c.bias, True)
         if self.pool:
             x = ops.maxpool2x2(x)
         return x
@@ -122,7 +123,8 @@ class VGG(nn.Module):
                 params += [cv.weight, cv.bias]
             trainable = torch.is_grad_enabled() and any(p.requires_grad for p in params)
             if trainable or t.requires_grad:
-                t = p8.block(t, n, c, h, w, blk.pool, params)
+                with ops.anomaly_scope(name + ".0"):
+                    t = p8.block(t, n, c, h, w, blk.pool, params)
             else:
                 with torch.no_grad():
                     for i in range(blk.num_convs):
@@ -136,7 +138,8 @@ class VGG(nn.Module):
             if blk.pool:
                 h, w = h // 2, w // 2
             if name in self._out_features:
-                outputs[name] = p8._ToNCHW.apply(t, n, c, h, w)
+                with ops.anomaly_scope(name):
+                    outputs[name] = p8._ToNCHW.apply(t, n, c, h, w)
         return outputs
 
     def forward(self, x):
@@ -146,11 +149,12 @@ class VGG(nn.Module):
         for name in self._names:
             block = getattr(self, name)[0]
             frozen = not any(p.requires_grad for p in block.parameters())
-            if frozen and not x.requires_grad:
-                with torch.no_grad():
+            with ops.anomaly_scope(name + ".0"):          # (the state-dict path of the block's module: vgg_block{b}.0.conv{k})
+                if frozen and not x.requires_grad:
+                    with torch.no_grad():
+                        x = block(x)
+                else:
                     x = block(x)
-            else:
-                x = block(x)
             if name in self._out_features:
                 outputs[name] = x
         return outputs

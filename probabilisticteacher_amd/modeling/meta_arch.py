@@ -80,10 +80,14 @@ class GuassianGeneralizedRCNN(nn.Module):
         assert self.can_run_jointly(sup_inputs, unsup_inputs)
         ns = len(sup_inputs)
         images = self.preprocess_image(list(sup_inputs) + list(unsup_inputs))
-        features = self.backbone(images.tensor)
-        feats = [features[f] for f in self.proposal_generator.in_features]
-        obj, deltas = self.proposal_generator.head_outputs(feats)
-        all_props = self.proposal_generator.proposals_from_head(images, features, (obj, deltas))
+        # (anomaly mode: the shared backbone + RPN-head pass reports as branch "joint", each branch's heads under its own name)
+        with ops.anomaly_branch("joint"):
+            with ops.anomaly_scope("backbone"):
+                features = self.backbone(images.tensor)
+            feats = [features[f] for f in self.proposal_generator.in_features]
+            with ops.anomaly_scope("proposal_generator"):
+                obj, deltas = self.proposal_generator.head_outputs(feats)
+                all_props = self.proposal_generator.proposals_from_head(images, features, (obj, deltas))
         out = []
         for sl, inputs, branch, da in ((slice(0, ns), sup_inputs, "supervised", False),
                                        (slice(ns, None), unsup_inputs, "unsupervised", danchor)):
@@ -91,9 +95,12 @@ class GuassianGeneralizedRCNN(nn.Module):
             feat = {k: v[sl] for k, v in features.items()}
             head = ([o[sl] for o in obj], [d[sl] for d in deltas])
             gt = [x["instances"].to(self.device) for x in inputs]
-            proposals, l_rpn = self.proposal_generator(img, feat, gt, branch=branch if branch == "unsupervised" else "",
-                                                       danchor=da, head_out=head, proposals=all_props[sl])
-            _, l_det = self.roi_heads(img, feat, proposals, gt, branch=branch)
+            with ops.anomaly_branch(branch):
+                with ops.anomaly_scope("proposal_generator"):
+                    proposals, l_rpn = self.proposal_generator(img, feat, gt, branch=branch if branch == "unsupervised" else "",
+                                                               danchor=da, head_out=head, proposals=all_props[sl])
+                with ops.anomaly_scope("roi_heads"):
+                    _, l_det = self.roi_heads(img, feat, proposals, gt, branch=branch)
             losses = {}
             losses.update(l_det)
             losses.update(l_rpn)
@@ -103,28 +110,39 @@ class GuassianGeneralizedRCNN(nn.Module):
     def forward(self, batched_inputs, branch="supervised", danchor=False):
         if not self.training:
             return self.inference(batched_inputs)
+        with ops.anomaly_branch(branch):
+            return self._forward_train(batched_inputs, branch, danchor)
+
+    def _forward_train(self, batched_inputs, branch, danchor):
         images = self.preprocess_image(batched_inputs)
         gt_instances = None
         if "instances" in batched_inputs[0]:
             gt_instances = [x["instances"].to(self.device) for x in batched_inputs]
-        features = self.backbone(images.tensor)
+        with ops.anomaly_scope("backbone"):
+            features = self.backbone(images.tensor)
 
         if branch == "supervised":
-            proposals_rpn, proposal_losses = self.proposal_generator(images, features, gt_instances)
-            _, detector_losses = self.roi_heads(images, features, proposals_rpn, gt_instances, branch=branch)
+            with ops.anomaly_scope("proposal_generator"):
+                proposals_rpn, proposal_losses = self.proposal_generator(images, features, gt_instances)
+            with ops.anomaly_scope("roi_heads"):
+                _, detector_losses = self.roi_heads(images, features, proposals_rpn, gt_instances, branch=branch)
             losses = {}
             losses.update(detector_losses)
             losses.update(proposal_losses)
             return losses, [], [], None
         if branch == "unsup_data_weak":
-            proposals_rpn, _ = self.proposal_generator(images, features, None, compute_loss=False)
-            proposals_roih, roi_predictions = self.roi_heads(images, features, proposals_rpn, targets=None,
-                                                             compute_loss=False, branch=branch)
+            with ops.anomaly_scope("proposal_generator"):
+                proposals_rpn, _ = self.proposal_generator(images, features, None, compute_loss=False)
+            with ops.anomaly_scope("roi_heads"):
+                proposals_roih, roi_predictions = self.roi_heads(images, features, proposals_rpn, targets=None,
+                                                                 compute_loss=False, branch=branch)
             return {}, proposals_rpn, proposals_roih, roi_predictions
         if branch == "unsupervised":
-            proposals_rpn, proposal_losses = self.proposal_generator(images, features, gt_instances, branch=branch,
-                                                                     danchor=danchor)
-            _, detector_losses = self.roi_heads(images, features, proposals_rpn, gt_instances, branch=branch)
+            with ops.anomaly_scope("proposal_generator"):
+                proposals_rpn, proposal_losses = self.proposal_generator(images, features, gt_instances, branch=branch,
+                                                                         danchor=danchor)
+            with ops.anomaly_scope("roi_heads"):
+                _, detector_losses = self.roi_heads(images, features, proposals_rpn, gt_instances, branch=branch)
             losses = {}
             losses.update(detector_losses)
             losses.update(proposal_losses)

@@ -116,7 +116,8 @@ class FastRCNNConvFCHead(nn.Module):
         if isinstance(x, DeferredROIAlign):
             from .. import p8
             if self.num_fc and self.fc1.weight.shape[1] >= p8.LINEAR_MIN_K:
-                x = p8.roi_align_linear(x.feat, x.rois, x.img_offsets, x.output_size, x.scale, self.fc1.weight, self.fc1.bias, True)
+                with ops.anomaly_scope("fc1"):        # (the fused node: box_pooler's ROIAlign + fc1)
+                    x = p8.roi_align_linear(x.feat, x.rois, x.img_offsets, x.output_size, x.scale, self.fc1.weight, self.fc1.bias, True)
                 first = 1
             else:
                 x = x.materialize()
@@ -124,7 +125,8 @@ class FastRCNNConvFCHead(nn.Module):
             x = x.flatten(1)
         for k in range(first, self.num_fc):
             fc = getattr(self, f"fc{k + 1}")
-            x = ops.linear(x, fc.weight, fc.bias, True)
+            with ops.anomaly_scope(f"fc{k + 1}"):
+                x = ops.linear(x, fc.weight, fc.bias, True)
         return x
 
 
@@ -192,8 +194,10 @@ class GuassianFastRCNNOutputLayers(nn.Module):
     nms_by_class: Optional[bool] = None     # inference(): None = by size (select_nms_by_class), True / False force a path
 
     def forward(self, x):
-        return (ops.linear(x, self.cls_score.weight, self.cls_score.bias, False),
-                ops.linear(x, self.bbox_pred.weight, self.bbox_pred.bias, False))
+        with ops.anomaly_scope("cls_score"):
+            scores = ops.linear(x, self.cls_score.weight, self.cls_score.bias, False)
+        with ops.anomaly_scope("bbox_pred"):
+            return scores, ops.linear(x, self.bbox_pred.weight, self.bbox_pred.bias, False)
 
     # ---- supervised (D2 FastRCNNOutputLayers.losses + fast_rcnn.py:265-336)
     def losses(self, predictions, proposals: List[FreeInstances]):
@@ -204,11 +208,13 @@ class GuassianFastRCNNOutputLayers(nn.Module):
         gb = torch.cat([p.gt_boxes.tensor for p in proposals], 0)
         if self.statistics is not None:                     # D2 0.5 _log_classification_stats, as device counts
             self.statistics.put_classification(ops.cls_stats(scores, gt_classes), gt_classes.numel())
-        loss_cls = ops.softmax_ce_mean(scores, gt_classes)
+        with ops.anomaly_scope("loss_cls"):
+            loss_cls = ops.softmax_ce_mean(scores, gt_classes)
         fg = torch.nonzero((gt_classes >= 0) & (gt_classes < K)).squeeze(1)
         d = deltas.view(-1, K, 8)[fg, gt_classes[fg]]
-        tgt = self.box2box_transform.get_deltas(pb[fg], gb[fg])
-        loss_box = self.nll_loss(d, tgt, 1.0 / max(gt_classes.numel(), 1.0))
+        with ops.anomaly_scope("loss_box_reg"):
+            tgt = self.box2box_transform.get_deltas(pb[fg], gb[fg])
+            loss_box = self.nll_loss(d, tgt, 1.0 / max(gt_classes.numel(), 1.0))
         out = {"loss_cls": loss_cls, "loss_box_reg": loss_box}
         return {k: v * self.loss_weight.get(k, 1.0) for k, v in out.items()}
 
@@ -219,7 +225,8 @@ class GuassianFastRCNNOutputLayers(nn.Module):
         T = torch.cat([p.soft_label for p in proposals]).detach().contiguous()
         r = T.shape[0]
         inv = 1.0 / r if r > 0 else float("nan")                      # fast_rcnn.py:209 divides by R
-        out = {"loss_cls": ops.soft_ce_efl(T, scores, U.TAU[0], U.EFL_LAMBDA[0], bool(U.EFL), inv)}
+        with ops.anomaly_scope("loss_cls"):
+            out = {"loss_cls": ops.soft_ce_efl(T, scores, U.TAU[0], U.EFL_LAMBDA[0], bool(U.EFL), inv)}
         if proposals[0].has("boxes_sigma"):
             with torch.no_grad():
                 sig_p = torch.cat([p.boxes_sigma for p in proposals])
@@ -227,10 +234,12 @@ class GuassianFastRCNNOutputLayers(nn.Module):
                 psb = torch.cat([p.pseudo_boxes.tensor for p in proposals])
                 cls = T.max(-1)[1] if r > 0 else torch.zeros(0, dtype=torch.int64, device=T.device)
                 rows = torch.nonzero(cls != K).squeeze(1)
-                mu_p = self.box2box_transform.get_deltas(pb[rows], psb[rows])
+                with ops.anomaly_scope("loss_box_reg"):
+                    mu_p = self.box2box_transform.get_deltas(pb[rows], psb[rows])
                 sig_sel = sig_p[rows].contiguous()
             q = deltas.view(-1, K, 8)[rows, cls[rows]]                 # one gather instead of the per-row loop (:159-161)
-            out["loss_box_reg"] = self.kl_loss(q, mu_p, sig_sel, None, U.TAU[1], U.EFL_LAMBDA[1], bool(U.EFL), 1, 1.0)
+            with ops.anomaly_scope("loss_box_reg"):
+                out["loss_box_reg"] = self.kl_loss(q, mu_p, sig_sel, None, U.TAU[1], U.EFL_LAMBDA[1], bool(U.EFL), 1, 1.0)
         return out
 
     # ---- teacher inference (fast_rcnn.py:338-409, :34-141)
@@ -365,15 +374,21 @@ class GuassianROIHead(nn.Module):
             assert targets
             proposals = self.label_and_sample_proposals(proposals, targets, branch=branch)
         feats = [features[f] for f in self.box_in_features]
-        box_features = self.box_pooler(feats, [x.proposal_boxes for x in proposals])
-        if isinstance(box_features, DeferredROIAlign) and not getattr(self.box_head, "accepts_deferred_roi_align", False):
-            box_features = box_features.materialize()       # any other head registered in ROI_BOX_HEAD_REGISTRY gets a tensor
-        predictions = self.box_predictor(self.box_head(box_features))
+        with ops.anomaly_scope("box_pooler"):
+            box_features = self.box_pooler(feats, [x.proposal_boxes for x in proposals])
+            if isinstance(box_features, DeferredROIAlign) and not getattr(self.box_head, "accepts_deferred_roi_align", False):
+                box_features = box_features.materialize()       # any other head registered in ROI_BOX_HEAD_REGISTRY gets a tensor
+        with ops.anomaly_scope("box_head"):
+            box_features = self.box_head(box_features)
+        with ops.anomaly_scope("box_predictor"):
+            predictions = self.box_predictor(box_features)
         del box_features
         if branch == "unsupervised" and self.training:
-            return proposals, self.box_predictor.losses_unsupervised(predictions, proposals)
+            with ops.anomaly_scope("box_predictor"):
+                return proposals, self.box_predictor.losses_unsupervised(predictions, proposals)
         if self.training and compute_loss:
-            return proposals, self.box_predictor.losses(predictions, proposals)
+            with ops.anomaly_scope("box_predictor"):
+                return proposals, self.box_predictor.losses(predictions, proposals)
         pred_instances, _ = self.box_predictor.inference(predictions, proposals)
         return pred_instances, predictions
 

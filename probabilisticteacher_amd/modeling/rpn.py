@@ -46,9 +46,12 @@ class GuassianRPNHead(nn.Module):
         """D2's StandardRPNHead interface: lists of (N, A, H, W) logits and (N, 8A, H, W) deltas"""
         obj, deltas = [], []
         for x in features:
-            t = ops.conv3x3(x, self.conv.weight, self.conv.bias, True)
-            obj.append(ops.conv1x1(t, self.objectness_logits.weight, self.objectness_logits.bias))
-            deltas.append(ops.conv1x1(t, self.anchor_deltas.weight, self.anchor_deltas.bias))
+            with ops.anomaly_scope("conv"):
+                t = ops.conv3x3(x, self.conv.weight, self.conv.bias, True)
+            with ops.anomaly_scope("objectness_logits"):
+                obj.append(ops.conv1x1(t, self.objectness_logits.weight, self.objectness_logits.bias))
+            with ops.anomaly_scope("anchor_deltas"):
+                deltas.append(ops.conv1x1(t, self.anchor_deltas.weight, self.anchor_deltas.bias))
         return obj, deltas
 
     def forward_flat(self, features: List[torch.Tensor]):
@@ -57,7 +60,9 @@ class GuassianRPNHead(nn.Module):
         permute copies).  GuassianRPN uses this method when the head has it."""
         obj, deltas = [], []
         for x in features:
-            t = ops.conv3x3(x, self.conv.weight, self.conv.bias, True)
+            with ops.anomaly_scope("conv"):
+                t = ops.conv3x3(x, self.conv.weight, self.conv.bias, True)
+            # (the fused node labels its two results objectness_logits / anchor_deltas itself)
             lg, d8 = ops.rpn_head_1x1(t, self.objectness_logits.weight, self.objectness_logits.bias,
                                       self.anchor_deltas.weight, self.anchor_deltas.bias)
             obj.append(lg)
@@ -136,7 +141,8 @@ class GuassianRPN(nn.Module):
     def head_outputs(self, feats):
         """the head's outputs in the flat anchor-order layout when the head offers it (no permute copies), else D2's"""
         flat = getattr(self.rpn_head, "forward_flat", None)
-        return flat(feats) if flat is not None else self.rpn_head(feats)
+        with ops.anomaly_scope("rpn_head"):
+            return flat(feats) if flat is not None else self.rpn_head(feats)
 
     # ------------------------------------------------------------------ forward (rpn.py:80-154)
     @staticmethod
@@ -225,11 +231,13 @@ class GuassianRPN(nn.Module):
             # (positives only exist for images with ground truth, so the gather index is always in range)
             gt_rows = gt_all[midx.view(-1)[flat_pos] + gt_off[img].long()]
         inv = 1.0 / (self.batch_size_per_image * n)
-        loss_cls = ops.bce_logits_sum(logits.contiguous(), lab_all, inv)
+        with ops.anomaly_scope("loss_rpn_cls"):
+            loss_cls = ops.bce_logits_sum(logits.contiguous(), lab_all, inv)
         d_rows = d8.reshape(-1, 8)[flat_pos]
         a_rows = anchors[flat_pos % r]
-        tgt = self.box2box_transform.get_deltas(a_rows, gt_rows)
-        loss_loc = self.nll_loss(d_rows, tgt, inv)
+        with ops.anomaly_scope("loss_rpn_loc"):
+            tgt = self.box2box_transform.get_deltas(a_rows, gt_rows)
+            loss_loc = self.nll_loss(d_rows, tgt, inv)
         return {"loss_rpn_cls": loss_cls, "loss_rpn_loc": loss_loc}
 
     # ------------------------------------------------------------------ unsupervised (rpn.py:257-361, 426-430)
@@ -253,12 +261,14 @@ class GuassianRPN(nn.Module):
             tgt_all = pb_all[sel]
         inv = 1.0 / (self.batch_size_per_image * n)
         x = logits.reshape(-1)[flat]
-        loss_cls, fg = ops.rpn_soft_obj_loss(T, x, U.TAU[0], U.EFL_LAMBDA[0], bool(U.EFL), inv)
+        with ops.anomaly_scope("loss_rpn_cls"):
+            loss_cls, fg = ops.rpn_soft_obj_loss(T, x, U.TAU[0], U.EFL_LAMBDA[0], bool(U.EFL), inv)
         out = {"loss_rpn_cls": loss_cls}
         if has_box:
             q = d8.reshape(-1, 8)[flat]
-            mu_p = self.box2box_transform.get_deltas(anchors[flat % r], tgt_all)
-            out["loss_rpn_loc"] = self.kl_loss(q, mu_p, sig_all, fg, U.TAU[1], U.EFL_LAMBDA[1], bool(U.EFL), 0, inv)
+            with ops.anomaly_scope("loss_rpn_loc"):
+                mu_p = self.box2box_transform.get_deltas(anchors[flat % r], tgt_all)
+                out["loss_rpn_loc"] = self.kl_loss(q, mu_p, sig_all, fg, U.TAU[1], U.EFL_LAMBDA[1], bool(U.EFL), 0, inv)
         return out
 
 

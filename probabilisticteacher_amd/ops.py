@@ -167,6 +167,98 @@ def deterministic(flag: bool = True):
         _DETERMINISTIC = prev
 
 
+# ============================================================================ anomaly mode (PTrainer(detect_anomaly=True))
+# With a sink (probabilisticteacher_amd/anomaly.py: AnomalySink) every autograd Function below and in p8.py scans each tensor it
+# returns from forward and each gradient it returns from backward -- one ptmi_nonfinite_scan launch per tensor into the sink's next
+# slot.  Like the two flags above the sink belongs to a trainer, which applies it around each of its steps.  Without one a
+# Function pays one `is None` test and executes the statements it executed before: no launch, no allocation.
+# Labels: modules push scope names (anomaly_scope) and the model pushes the branch (anomaly_branch); a Function remembers the
+# labels of its forward on its ctx, so that its backward -- which runs outside every `with` -- reports under the same path.
+_ANOMALY = None
+_ANOMALY_SCOPES: List[str] = []
+_ANOMALY_BRANCHES: List[str] = []
+
+
+@contextlib.contextmanager
+def anomaly(sink):
+    """Scope an anomaly sink (None = off); restores the previous one on exit."""
+    global _ANOMALY
+    prev = _ANOMALY
+    _ANOMALY = sink
+    try:
+        yield sink
+    finally:
+        _ANOMALY = prev
+
+
+@contextlib.contextmanager
+def anomaly_scope(name: str):
+    """Push a scope label ("backbone", "vgg_block5.0", ...: joined with dots they read like a state-dict path) for the scans made
+    inside; a no-op without a sink."""
+    if _ANOMALY is None:
+        yield
+        return
+    _ANOMALY_SCOPES.append(name)
+    try:
+        yield
+    finally:
+        _ANOMALY_SCOPES.pop()
+
+
+@contextlib.contextmanager
+def anomaly_branch(name: str):
+    """the model's branch ("supervised", "unsupervised", "unsup_data_weak", "joint") for the scans made inside; the innermost
+    one counts.  A no-op without a sink."""
+    if _ANOMALY is None:
+        yield
+        return
+    _ANOMALY_BRANCHES.append(name)
+    try:
+        yield
+    finally:
+        _ANOMALY_BRANCHES.pop()
+
+
+def anomaly_labels() -> Tuple[str, str]:
+    """(branch, scope path) in force"""
+    return (_ANOMALY_BRANCHES[-1] if _ANOMALY_BRANCHES else "", ".".join(_ANOMALY_SCOPES))
+
+
+def _anomaly_scan(where: Tuple[str, str], phase: str, op: str, items) -> None:
+    """items: (output name, tensor or None[, scope suffix[, P8 (n, c, h, w)]]) in the order the launches produced them"""
+    branch, scope = where
+    for item in items:
+        name, t = item[0], item[1]
+        if t is None:
+            continue
+        sub = item[2] if len(item) > 2 else None
+        _ANOMALY.scan(t, phase, op, name, branch, (scope + "." + sub if scope else sub) if sub else scope,
+                      item[3] if len(item) > 3 else None)
+
+
+def _anomaly_fwd(ctx, op: str, items) -> None:
+    """a Function's forward, sink active: remember the labels for backward, scan the results"""
+    ctx.anomaly_where = where = anomaly_labels()
+    _anomaly_scan(where, "forward", op, items)
+
+
+def _anomaly_bwd(ctx, op: str, items) -> None:
+    """a Function's backward, sink active: scan the gradients it returns under the labels of its forward"""
+    _anomaly_scan(getattr(ctx, "anomaly_where", None) or anomaly_labels(), "backward", op, items)
+
+
+def seg_nonfinite(g: torch.Tensor, table: "SegmentTable", seg_flags: torch.Tensor) -> torch.Tensor:
+    """seg_flags[:S] (int32) = 1 if segment i of the flat gradient holds a NaN, | 2 if it holds an infinity (ptmi_seg_nonfinite);
+    cleared by the entry point first; g is not written."""
+    table.check(g)
+    _chk(seg_flags, torch.int32, "seg_flags")
+    if seg_flags.numel() < table.S:
+        raise ValueError(f"seg_flags holds {seg_flags.numel()} words for {table.S} segments")
+    _lib.call("ptmi_seg_nonfinite", _ptr(g), g.numel(), _ptr(table.seg_off), table.S, _ptr(table.chunks), table.C, _ptr(seg_flags),
+              _stream())
+    return seg_flags[: table.S]
+
+
 def _rnd(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     if _OPERAND_ROUNDING != "bf16_emulate" or t is None:
         return t
@@ -505,6 +597,8 @@ class _Conv3x3(torch.autograd.Function):
         y = _rnd_stored(conv3x3_raw(x, wp, bias, None, weight.shape[0], 1 if relu else 0))
         ctx.relu = relu
         ctx.save_for_backward(x, weight, y if relu else None)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "conv3x3", (("y", y),))
         return y
 
     @staticmethod
@@ -520,6 +614,8 @@ class _Conv3x3(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             wpd = conv3x3_pack(weight, 1, 2, (h, w))
             dx = _rnd_stored(conv3x3_raw(dz, wpd, None, None, cin, 2))
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "conv3x3", (("dw", dw), ("db", db), ("dx", dx)))
         return dx, dw, db, None
 
 
@@ -540,6 +636,8 @@ class _MaxPool2x2(torch.autograd.Function):
         with _prof("maxpool_fwd"):
             _lib.call("ptmi_maxpool2x2_fwd", _ptr(x), _ptr(y), n * c, h, w, _stream())
         ctx.save_for_backward(x)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "maxpool2x2", (("y", y),))
         return y
 
     @staticmethod
@@ -548,6 +646,8 @@ class _MaxPool2x2(torch.autograd.Function):
         n, c, h, w = x.shape
         dx = torch.empty_like(x)
         _lib.call("ptmi_maxpool2x2_bwd", _ptr(x), _ptr(_chk(dy.contiguous())), _ptr(dx), n * c, h, w, 0, _stream())
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "maxpool2x2", (("dx", dx),))
         return dx
 
 
@@ -580,6 +680,9 @@ class _VGGBlock(torch.autograd.Function):
             out = pooled
         ctx.k, ctx.pool = k, pool
         ctx.save_for_backward(*acts, *ws)
+        if _ANOMALY is not None:        # layer granularity: the node covers a whole block
+            _anomaly_fwd(ctx, "vgg_block", [("y", acts[j], f"conv{j}") for j in range(1, k + 1)] +
+                         ([("pooled", out)] if pool else []))
         return out
 
     @staticmethod
@@ -597,6 +700,7 @@ class _VGGBlock(torch.autograd.Function):
             dz = relu_bwd(dout, yk)
         grads = [None] * (2 * k)
         dx = None
+        seen = None if _ANOMALY is None else [("dz", dz, f"conv{k}")]
         for j in range(k, 0, -1):
             xin, w = acts[j - 1], ws[j - 1]
             n, cin, h, wd = xin.shape
@@ -604,10 +708,18 @@ class _VGGBlock(torch.autograd.Function):
             if ctx.needs_input_grad[2 + 2 * (j - 1)] or ctx.needs_input_grad[3 + 2 * (j - 1)]:
                 dw, db = conv3x3_wgrad(xin, dz, cout)
                 grads[2 * (j - 1)], grads[2 * (j - 1) + 1] = dw, db
+                if seen is not None:
+                    seen += [("dw", dw, f"conv{j}"), ("db", db, f"conv{j}")]
             if j > 1:
                 dz = conv3x3_raw(dz, conv3x3_pack(w, 1, 3, (h, wd)), None, xin, cin, 3)      # dgrad + ReLU mask of layer j-1
+                if seen is not None:
+                    seen.append(("dz", dz, f"conv{j - 1}"))
             elif ctx.needs_input_grad[0]:
                 dx = conv3x3_raw(dz, conv3x3_pack(w, 1, 2, (h, wd)), None, None, cin, 2)
+                if seen is not None:
+                    seen.append(("dx", dx, "conv1"))
+        if seen is not None:
+            _anomaly_bwd(ctx, "vgg_block", seen)
         return (dx, None, *grads)
 
 
@@ -665,6 +777,8 @@ class _Linear(torch.autograd.Function):
         y = gemm(x, weight, r, nout, k, k, k, 0, 1, bias=bias, bias_mode=2, relu=relu)
         ctx.relu = relu
         ctx.save_for_backward(x, weight, y if relu else None)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "linear", (("y", y),))
         return y
 
     @staticmethod
@@ -684,6 +798,8 @@ class _Linear(torch.autograd.Function):
                 dw = gemm(dz, x, nout, k, r, nout, k, 1, 0)                   # dz^T (nout,r) x x (r,k)
         if ctx.needs_input_grad[2]:
             db = colsum(dz)
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "linear", (("dx", dx), ("dw", dw), ("db", db)))
         return dx, dw, db, None
 
 
@@ -710,6 +826,8 @@ class _Conv1x1(torch.autograd.Function):
              stride_b=ci * hw, stride_c=co * hw, ldc=hw)
         ctx.save_for_backward(x, w2)
         ctx.wshape = weight.shape
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "conv1x1", (("y", y),))
         return y
 
     @staticmethod
@@ -731,6 +849,8 @@ class _Conv1x1(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             db = torch.empty(co, dtype=F32, device=x.device)
             _lib.call("ptmi_rowsum_batched", _ptr(dy), _ptr(db), n, co, hw, 0, _stream())
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "conv1x1", (("dx", dx), ("dw", dw), ("db", db)))
         return dx, dw, db
 
 
@@ -759,6 +879,8 @@ class _RPNHead1x1(torch.autograd.Function):
         ctx.save_for_backward(x, *w2s)
         ctx.shapes = (w_obj.shape, w_del.shape)
         a = w_obj.shape[0]
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "rpn_head_1x1", (("logits", outs[0], "objectness_logits"), ("deltas", outs[1], "anchor_deltas")))
         return outs[0].view(n, hw * a), outs[1].view(n, hw * a, 8)
 
     @staticmethod
@@ -783,6 +905,9 @@ class _RPNHead1x1(torch.autograd.Function):
             part = gemm(dy, x, co, ci, hw, co, hw, 1, 1, batch=n, stride_a=hw * co, stride_b=ci * hw, stride_c=co * ci)
             grads.append(colsum(part.view(n, co * ci)).view(shape))
             grads.append(colsum(dy.view(n * hw, co)))
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "rpn_head_1x1", (("dw", grads[0], "objectness_logits"), ("db", grads[1], "objectness_logits"),
+                                               ("dw", grads[2], "anchor_deltas"), ("db", grads[3], "anchor_deltas"), ("dx", dx)))
         return dx, grads[0], grads[1], grads[2], grads[3]
 
 
@@ -823,6 +948,8 @@ class _ROIAlign(torch.autograd.Function):
                           _stream(), *var)
         ctx.save_for_backward(rois, img_offsets)
         ctx.meta = (n, c, h, w, pooled, float(scale), aligned, sampling_ratio)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "roi_align", (("out", out),))
         return out
 
     @staticmethod
@@ -841,6 +968,8 @@ class _ROIAlign(torch.autograd.Function):
             with _prof("roi_align_bwd"):
                 _lib.call("ptmi_roi_align_bwd" + sfx, _ptr(dout), _ptr(rois), _ptr(dfeat), n, c, h, w, rois.shape[0], pooled,
                           scale, _stream(), *var)
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "roi_align", (("dfeat", dfeat),))
         return dfeat, None, None, None, None, None, None
 
 
@@ -949,6 +1078,8 @@ class _ROIPool(torch.autograd.Function):
         ctx.save_for_backward(rois, argmax)
         ctx.meta = (n, c, h, w, pooled)
         ctx.mark_non_differentiable(argmax)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "roi_pool", (("out", out),))
         return out, argmax
 
     @staticmethod
@@ -957,11 +1088,16 @@ class _ROIPool(torch.autograd.Function):
         n, c, h, w, pooled = ctx.meta
         dout = _chk(dout.contiguous())
         if _DETERMINISTIC:
-            return roi_pool_bwd_det(dout, argmax, rois, ctx.img_offsets, n, c, h, w, pooled), None, None, None, None
+            dfeat = roi_pool_bwd_det(dout, argmax, rois, ctx.img_offsets, n, c, h, w, pooled)
+            if _ANOMALY is not None:
+                _anomaly_bwd(ctx, "roi_pool", (("dfeat", dfeat),))
+            return dfeat, None, None, None, None
         dfeat = torch.empty((n, c, h, w), dtype=F32, device=dout.device)        # (zeroed by the entry point)
         with _prof("roi_pool_bwd"):
             _lib.call("ptmi_roi_pool_bwd", _ptr(dout), _ptr(argmax), _ptr(rois), _ptr(dfeat), n, c, h, w, rois.shape[0], pooled,
                       _stream())
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "roi_pool", (("dfeat", dfeat),))
         return dfeat, None, None, None, None
 
 
@@ -1009,6 +1145,8 @@ class _GetDeltas(torch.autograd.Function):
             _lib.call("ptmi_get_deltas", _ptr(src), _ptr(tgt), _ptr(out), src.shape[0], wx, wy, ww, wh, _stream())
         ctx.save_for_backward(src, tgt)
         ctx.w = (wx, wy, ww, wh)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "get_deltas", (("deltas", out),))
         return out
 
     @staticmethod
@@ -1018,12 +1156,17 @@ class _GetDeltas(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             rows = src.shape[0]
             if _DETERMINISTIC:          # row i is its own destination: the identity form of the fixed-order entry
-                return get_deltas_bwd_src_det(src, tgt, dd, None, rows, ctx.w), None, None, None, None, None
+                dsrc = get_deltas_bwd_src_det(src, tgt, dd, None, rows, ctx.w)
+                if _ANOMALY is not None:
+                    _anomaly_bwd(ctx, "get_deltas", (("dsrc", dsrc),))
+                return dsrc, None, None, None, None, None
             dsrc = torch.zeros_like(src)
             if rows:
                 idx = torch.arange(rows, dtype=torch.int64, device=src.device)
                 _lib.call("ptmi_get_deltas_bwd_src", _ptr(src), _ptr(tgt), _ptr(_chk(dd.contiguous())), _ptr(idx), rows,
                           *ctx.w, _ptr(dsrc), _stream())
+            if _ANOMALY is not None:
+                _anomaly_bwd(ctx, "get_deltas", (("dsrc", dsrc),))
         return dsrc, None, None, None, None, None
 
 
@@ -1386,11 +1529,17 @@ class _BCELogitsSum(torch.autograd.Function):
         _lib.call("ptmi_bce_logits_sum", _ptr(logits), _ptr(labels), logits.numel(), float(inv_norm), _ptr(loss),
                   _ptr(dl), _ptr(_loss_ws(logits.device)), _stream())
         ctx.save_for_backward(dl)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "bce_logits_sum", (("loss", loss),))
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
+        if _ANOMALY is not None:
+            out = dl * g
+            _anomaly_bwd(ctx, "bce_logits_sum", (("dlogits", out),))
+            return out, None, None
         return dl * g, None, None
 
 
@@ -1410,6 +1559,8 @@ def _nll_sum_forward(ctx, entry: str, d, t, inv_norm: float):
               _ptr(_loss_ws(d.device)), _stream())
     ctx.has_dt = dt is not None
     ctx.save_for_backward(dd, dt) if dt is not None else ctx.save_for_backward(dd)
+    if _ANOMALY is not None:
+        _anomaly_fwd(ctx, entry[5:], (("loss", loss),))
     return loss.reshape(())
 
 
@@ -1422,9 +1573,13 @@ class _GaussianNLLSum(torch.autograd.Function):
     def backward(ctx, g):
         if ctx.has_dt:
             dd, dt = ctx.saved_tensors
-            return dd * g, dt * g, None
-        (dd,) = ctx.saved_tensors
-        return dd * g, None, None
+            out = (dd * g, dt * g, None)
+        else:
+            (dd,) = ctx.saved_tensors
+            out = (dd * g, None, None)
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "nll_sum", (("ddeltas", out[0]), ("dtarget", out[1])))
+        return out
 
 
 def gaussian_nll_sum(d, t, inv_norm):
@@ -1454,11 +1609,17 @@ class _SoftmaxCEMean(torch.autograd.Function):
         _lib.call("ptmi_softmax_ce_mean", _ptr(logits), _ptr(target), r, c, _ptr(loss), _ptr(dl),
                   _ptr(_loss_ws(logits.device)), _stream())
         ctx.save_for_backward(dl)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "softmax_ce_mean", (("loss", loss),))
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
+        if _ANOMALY is not None:
+            out = dl * g
+            _anomaly_bwd(ctx, "softmax_ce_mean", (("dlogits", out),))
+            return out, None
         return dl * g, None
 
 
@@ -1508,11 +1669,17 @@ class _SoftCEEFL(torch.autograd.Function):
         _lib.call("ptmi_soft_ce_efl", _ptr(teacher), _ptr(student), r, c, float(tau), float(lam), int(efl),
                   float(inv_norm), _ptr(loss), _ptr(ds), _ptr(_loss_ws(student.device)), _stream())
         ctx.save_for_backward(ds)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "soft_ce_efl", (("loss", loss),))
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
         (ds,) = ctx.saved_tensors
+        if _ANOMALY is not None:
+            out = ds * g
+            _anomaly_bwd(ctx, "soft_ce_efl", (("dstudent", out),))
+            return None, out, None, None, None, None
         return None, ds * g, None, None, None, None
 
 
@@ -1533,11 +1700,17 @@ class _RPNSoftObj(torch.autograd.Function):
                   float(inv_norm), _ptr(loss), _ptr(dx), _ptr(fg), _ptr(_loss_ws(x.device)), _stream())
         ctx.save_for_backward(dx)
         ctx.mark_non_differentiable(fg)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "rpn_soft_obj_loss", (("loss", loss),))
         return loss.reshape(()), fg
 
     @staticmethod
     def backward(ctx, g, _gfg):
         (dx,) = ctx.saved_tensors
+        if _ANOMALY is not None:
+            out = dx * g
+            _anomaly_bwd(ctx, "rpn_soft_obj_loss", (("dx", out),))
+            return None, out, None, None, None, None
         return None, dx * g, None, None, None, None
 
 
@@ -1561,6 +1734,8 @@ def _kl_efl_forward(ctx, entry: str, q, mu_p, slog_p, fg, tau, lam, efl, reducti
               _ptr(_loss_ws(q.device)), _stream())
     ctx.has_dmu = dmu is not None
     ctx.save_for_backward(dq, dmu) if dmu is not None else ctx.save_for_backward(dq)
+    if _ANOMALY is not None:
+        _anomaly_fwd(ctx, entry[5:], (("loss", loss),))
     return loss.reshape(())
 
 
@@ -1573,9 +1748,13 @@ class _KLEFL(torch.autograd.Function):
     def backward(ctx, g):
         if ctx.has_dmu:
             dq, dmu = ctx.saved_tensors
-            return dq * g, dmu * g, None, None, None, None, None, None, None
-        (dq,) = ctx.saved_tensors
-        return dq * g, None, None, None, None, None, None, None, None
+            out = (dq * g, dmu * g)
+        else:
+            (dq,) = ctx.saved_tensors
+            out = (dq * g, None)
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "kl_efl_loss", (("dq", out[0]), ("dmu", out[1])))
+        return out[0], out[1], None, None, None, None, None, None, None
 
 
 def kl_efl_loss(q, mu_p, slog_p, fg, tau, lam, efl, reduction, inv_norm):

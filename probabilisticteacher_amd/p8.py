@@ -152,10 +152,18 @@ class _ToNCHW(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, n, c, h, w):
         ctx.meta = (n, c, h, w)
+        if ops._ANOMALY is not None:
+            y = to_nchw(t, n, c, h, w)
+            ops._anomaly_fwd(ctx, "p8_to_nchw", (("y", y),))
+            return y
         return to_nchw(t, n, c, h, w)
 
     @staticmethod
     def backward(ctx, dy):
+        if ops._ANOMALY is not None:
+            dt = from_nchw(dy)
+            ops._anomaly_bwd(ctx, "p8_to_nchw", (("dt", dt, None, ctx.meta),))
+            return dt, None, None, None, None
         return from_nchw(dy), None, None, None, None
 
 
@@ -163,10 +171,18 @@ class _FromNCHW(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         ctx.meta = tuple(x.shape)
+        if ops._ANOMALY is not None:
+            t = from_nchw(x)
+            ops._anomaly_fwd(ctx, "p8_from_nchw", (("t", t, None, ctx.meta),))
+            return t
         return from_nchw(x)
 
     @staticmethod
     def backward(ctx, dt):
+        if ops._ANOMALY is not None:
+            dx = to_nchw(dt.contiguous(), *ctx.meta)
+            ops._anomaly_bwd(ctx, "p8_from_nchw", (("dx", dx),))
+            return dx
         return to_nchw(dt.contiguous(), *ctx.meta)
 
 
@@ -187,6 +203,9 @@ class _Block(torch.autograd.Function):
         out = maxpool_fwd(acts[-1], n, c, h, w) if pool else acts[-1]
         ctx.meta = (k, pool, n, cin, h, w)
         ctx.save_for_backward(*acts, *ws)
+        if ops._ANOMALY is not None:        # layer granularity: the node covers a whole block
+            ops._anomaly_fwd(ctx, "p8_block", [("y", acts[j], f"conv{j}", (n, ws[j - 1].shape[0], h, w)) for j in range(1, k + 1)] +
+                             ([("pooled", out, None, (n, c, h // 2, w // 2))] if pool else []))
         return out
 
     @staticmethod
@@ -199,15 +218,24 @@ class _Block(torch.autograd.Function):
         dz = maxpool_bwd(acts[k], dout, n, cout, h, w, True) if pool else relu_bwd(dout, acts[k])
         grads = [None] * (2 * k)
         dx = None
+        seen = None if ops._ANOMALY is None else [("dz", dz, f"conv{k}", (n, cout, h, w))]
         for j in range(k, 0, -1):
             xin, wt = acts[j - 1], ws[j - 1]
             co, ci = wt.shape[0], wt.shape[1]
             if ctx.needs_input_grad[6 + 2 * (j - 1)] or ctx.needs_input_grad[7 + 2 * (j - 1)]:
                 grads[2 * (j - 1)], grads[2 * (j - 1) + 1] = wgrad(xin, dz, n, ci, co, h, w)
+                if seen is not None:
+                    seen += [("dw", grads[2 * (j - 1)], f"conv{j}"), ("db", grads[2 * (j - 1) + 1], f"conv{j}")]
             if j > 1:
                 dz = conv3x3_raw(dz, pack_weights(wt, 1), None, xin, n, co, ci, h, w, 3)       # dgrad + ReLU mask of layer j - 1
+                if seen is not None:
+                    seen.append(("dz", dz, f"conv{j - 1}", (n, ci, h, w)))
             elif ctx.needs_input_grad[0]:
                 dx = conv3x3_raw(dz, pack_weights(wt, 1), None, None, n, co, ci, h, w, 2)
+                if seen is not None:
+                    seen.append(("dx", dx, "conv1", (n, ci, h, w)))
+        if seen is not None:
+            ops._anomaly_bwd(ctx, "p8_block", seen)
         return (dx, None, None, None, None, None, *grads)
 
 
@@ -234,6 +262,8 @@ class _Conv(torch.autograd.Function):
         y = conv3x3_raw(x, pack_weights(weight, 0), bias, None, n, cin, weight.shape[0], h, w, 1 if relu else 0)
         ctx.meta = (n, cin, h, w, relu)
         ctx.save_for_backward(x, weight, y if relu else None)
+        if ops._ANOMALY is not None:
+            ops._anomaly_fwd(ctx, "p8_conv3x3", (("y", y, None, (n, weight.shape[0], h, w)),))
         return y
 
     @staticmethod
@@ -247,6 +277,8 @@ class _Conv(torch.autograd.Function):
             dw, db = wgrad(x, dz, n, cin, cout, h, w)
         if ctx.needs_input_grad[0]:
             dx = conv3x3_raw(dz, pack_weights(weight, 1), None, None, n, cout, cin, h, w, 2)
+        if ops._ANOMALY is not None:
+            ops._anomaly_bwd(ctx, "p8_conv3x3", (("dw", dw), ("db", db), ("dx", dx, None, (n, cin, h, w))))
         return dx, None, None, None, None, None, dw, db
 
 
@@ -313,6 +345,8 @@ class _LinearP8(torch.autograd.Function):
         xt = pack_matrix(x, k, r, k, False) if (recording and ctx.needs_input_grad[1]) else None
         ctx.meta = (r, k, n, relu, ctx.needs_input_grad[0])
         ctx.save_for_backward(xt, weight, y if relu else None)
+        if ops._ANOMALY is not None:
+            ops._anomaly_fwd(ctx, "p8_linear", (("y", y),))
         return y
 
     @staticmethod
@@ -328,6 +362,8 @@ class _LinearP8(torch.autograd.Function):
             dw = gemm_nt(pack_matrix(dz, n, r, n, False), xt, n, k, r)
         if ctx.needs_input_grad[2]:                        # the bias gradient sums the values the GEMMs consumed (rounded)
             db = ops.colsum(dz.to(BF16).to(F32))
+        if ops._ANOMALY is not None:
+            ops._anomaly_bwd(ctx, "p8_linear", (("dx", dx), ("dw", dw), ("db", db)))
         return dx, dw, db, None, None
 
 
@@ -346,6 +382,8 @@ class _RoiAlignLinearP8(torch.autograd.Function):
         y = gemm_nt(xk, pack_matrix(weight, n, k, k, True), r, n, k, bias, relu)
         ctx.meta = (r, k, n, relu, (n_img, c, h, w), pooled, float(scale))
         ctx.save_for_backward(xt, weight, y if relu else None, rois, img_offsets)
+        if ops._ANOMALY is not None:    # the pooled features exist only as the GEMM's bf16 operand (k octets x rows x 8)
+            ops._anomaly_fwd(ctx, "p8_roi_align_linear", (("pooled", xk), ("y", y)))
         return y
 
     @staticmethod
@@ -354,7 +392,7 @@ class _RoiAlignLinearP8(torch.autograd.Function):
         r, k, n, relu, (n_img, c, h, w), pooled, scale = ctx.meta
         dy = ops._chk(dy.contiguous())
         dz = ops.relu_bwd(dy, y) if relu else dy
-        dfeat = dw = db = None
+        dfeat = dw = db = dx = None
         if ctx.needs_input_grad[0]:
             dx = gemm_nt(pack_matrix(dz, r, n, n, True), pack_matrix(weight, k, n, k, False), r, k, n, swapped=True)
             dfeat = ops.roi_align_bwd_grouped(dx, rois, img_offsets, n_img, c, h, w, pooled, scale)
@@ -362,6 +400,8 @@ class _RoiAlignLinearP8(torch.autograd.Function):
             dw = gemm_nt(pack_matrix(dz, n, r, n, False), xt, n, k, r)
         if ctx.needs_input_grad[6]:
             db = ops.colsum(dz.to(BF16).to(F32))
+        if ops._ANOMALY is not None:
+            ops._anomaly_bwd(ctx, "p8_roi_align_linear", (("dpooled", dx), ("dfeat", dfeat), ("dw", dw), ("db", db)))
         return dfeat, None, None, None, None, dw, db, None, None
 
 

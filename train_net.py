@@ -46,6 +46,9 @@ def main():
     ap.add_argument("--eval-only", action="store_true")
     ap.add_argument("--no-statistics", action="store_true",
                     help="log the losses only, without the rpn/ roi_head/ fast_rcnn/ statistics of a reference run's metrics.json")
+    ap.add_argument("--detect-anomaly", action="store_true",
+                    help="the reference's torch.autograd.set_detect_anomaly: check every activation and gradient for NaN / inf, stop "
+                         "BEFORE the update of the first bad step; writes OUTPUT_DIR/anomaly.json and model_before_anomaly.pth")
     ap.add_argument("--register", action="append", default=[], metavar="NAME=DIR:SPLIT:CLS1,CLS2",
                     help="register a VOC-format directory as dataset NAME (Annotations/, JPEGImages/, ImageSets/Main/SPLIT.txt)")
     ap.add_argument("--register-coco", action="append", default=[], metavar="NAME=JSON:IMAGE_ROOT",
@@ -78,7 +81,7 @@ def main():
         loader = synthetic_loader(cfg, torch.device("cuda", local), rank, world)
     else:
         loader = PTrainer.build_train_loader(cfg)              # trainer.py:139-141 -> pt/data/build.py:107
-    trainer = PTrainer(cfg, data_loader=loader, statistics=not args.no_statistics)
+    trainer = PTrainer(cfg, data_loader=loader, statistics=not args.no_statistics, detect_anomaly=args.detect_anomaly)
     inc = trainer.resume_or_load(resume=args.resume)          # trainer.py:466-496 (no-op without MODEL.WEIGHTS / checkpoint)
     if inc is not None and rank == 0:
         print(f"loaded {cfg.MODEL.WEIGHTS or 'last_checkpoint'}: start_iter {trainer.start_iter}, "
@@ -102,7 +105,19 @@ def main():
             print({k: v for k, v in res.items() if k == "bbox"}, flush=True)
         return
     # periodic checkpoints, metrics.json, model_final.pth; the student / teacher eval hooks run on cfg.DATASETS.TEST
-    trainer.train(max_iter=args.max_iter, run_eval=not args.synthetic)
+    from probabilisticteacher_amd.anomaly import AnomalyError
+    try:
+        trainer.train(max_iter=args.max_iter, run_eval=not args.synthetic)
+    except AnomalyError as e:
+        # the step was stopped before its update: the weights on the device are the last good ones (iteration iter - 1)
+        if rank == 0:
+            from probabilisticteacher_amd import checkpoint
+            os.makedirs(cfg.OUTPUT_DIR, exist_ok=True)
+            with open(os.path.join(cfg.OUTPUT_DIR, "anomaly.json"), "w") as f:
+                f.write(e.to_json() + "\n")
+            checkpoint.save_checkpoint(trainer, os.path.join(cfg.OUTPUT_DIR, "model_before_anomaly.pth"),
+                                       iteration=trainer.iter - 1, tag_last=False)
+        sys.exit(f"AnomalyError: {e}")
     if world > 1:
         dist.destroy_process_group()
 
