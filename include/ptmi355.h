@@ -143,6 +143,40 @@ int ptmi_conv3x3_wino4p_fwd_sched(const float* x, const float* wp, const float* 
                                   const float* mask_ref, float* y, int n, int cin, int cout, int h,
                                   int w, int epilogue, int32_t* sched, ptmi_stream_t s);
 int ptmi_conv3x3_wino4p_fwd_fits(int cin, int cout, int h, int w);
+/* ------------------------------------------------------------------ the constant frame of a shrink-pasted image (csrc/frame_skip.h)
+ * PTrainer.resize (reference pt/engine/trainer.py:557-590) pastes every strong view, shrunk by r ~ U(0.5, 1), into the middle of a
+ * canvas of one colour.  Inside that frame every 3x3 layer's output is a fixed pattern y[c][y & 3][x & 3] (period 4: the 4x4 output
+ * tile of F(4x4, 3x3)); the entry points below let a forward launch leave those tiles out and write the pattern instead.
+ * A RING is eight int32 per image -- outer (x0, y0, x1, y1), inner (x0, y0, x1, y1), half-open, in the resolution of a layer's
+ * INPUT: every input pixel inside outer and outside inner holds the pattern; outer x1 <= x0 = the image has none.
+ * ptmi_frame_ring_next: the rings of a layer's output from those of its h x w input.  op 0: conv3x3 pad 1 by a direct kernel -- an
+ * output pixel is the pattern iff its 3x3 window is; op 1: max pool 2x2 / 2 (floor); op 2: conv3x3 by the F(4x4, 3x3) kernels -- the
+ * roundoff of a tile's sixteen outputs depends on its whole 6x6 window, so only whole tiles that ptmi_frame_tile_skippable accepts
+ * are the pattern BIT FOR BIT: outer shrinks and inner grows to tile boundaries.
+ * ptmi_frame_tile_skippable: 1 iff the 4x4 output tile at (py, px) of an h x w image reads only the pattern (its whole 6x6 window
+ * inside outer and outside inner) and lies inside the image.  ptmi_frame_pixel_tile_skippable: 1 iff all 32 tiles of pixel tile
+ * `pix` of the F(4x4, 3x3) walk (64 flat columns x 8 rows of the concatenated strips; ptmi_frame_pixel_tiles of them) are.
+ * ptmi_frame_skip_lists: the ascending lists of the pixel tiles to compute (keep) and to fill (skip), room for
+ * ptmi_frame_pixel_tiles ints each, counts[0] / counts[1] their lengths.  All of these run on the host and touch no device. */
+int ptmi_frame_ring_next(const int32_t* rings_in, int32_t* rings_out, int n, int op, int h, int w);
+int64_t ptmi_frame_pixel_tiles(int n, int h, int w);
+int ptmi_frame_tile_skippable(const int32_t* ring, int h, int w, int py, int px);
+int ptmi_frame_pixel_tile_skippable(const int32_t* rings, int n, int h, int w, int pix);
+int ptmi_frame_skip_lists(const int32_t* rings, int n, int h, int w, int32_t* keep, int32_t* skip,
+                          int32_t* counts);
+/* ptmi_conv3x3_wino4p_fwd over a LIST of pixel tiles (static schedule; a separate instantiation of the same kernel: a tile's
+ * arithmetic is the plain launch's, bit for bit): pix_list = n_list ascending pixel-tile numbers in device memory, e.g. `keep` of
+ * ptmi_frame_skip_lists.  Outputs of tiles outside the list are not written. */
+int ptmi_conv3x3_wino4p_fwd_list(const float* x, const float* wp, const float* bias,
+                                 const float* mask_ref, float* y, int n, int cin, int cout, int h, int w,
+                                 int epilogue, const int32_t* pix_list, int n_list, ptmi_stream_t s);
+/* Writes the outputs of the pixel tiles in skip_list (device memory, as `skip` of ptmi_frame_skip_lists for the rings `rings`, also
+ * in device memory, of the layer's INPUT): y[n][c][y][x] = pattern[c][y & 3][x & 3] (pattern: cout x 4 x 4 floats), with 16-byte
+ * stores.  pooled = 1: y is the (n, cout, h / 2, w / 2) output of epilogue 4 and the pattern is indexed by pooled coordinates.
+ * Every tile is tested against its ring before it is written.  Writes only tiles the list launch leaves out: the two may run in
+ * either order. */
+int ptmi_frame_fill(const int32_t* skip_list, int n_skip, const int32_t* rings, const float* pattern,
+                    float* y, int n, int cout, int h, int w, int pooled, ptmi_stream_t s);
 /* The two Winograd-domain weight-gradient kernels with `waves` fills of the chip's one-workgroup-per-CU slots instead of one
  * (round 6): their workgroups each own a contiguous share of the (image, tile) list, so with one fill a workgroup whose CU is held by
  * another kernel when the launch starts -- an RCCL collective overlapping backward, pt/engine/trainer.py:92-95,384 under DDP --

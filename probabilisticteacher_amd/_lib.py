@@ -41,6 +41,13 @@ SIGNATURES = {
     "ptmi_conv3x3_wino4p_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ptmi_conv3x3_wino4p_fwd_sched": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ptmi_conv3x3_wino4p_fwd_fits": (_i, [_i, _i, _i, _i]),
+    "ptmi_frame_ring_next": (_i, [_vp, _vp, _i, _i, _i, _i]),
+    "ptmi_frame_pixel_tiles": (_i64, [_i, _i, _i]),
+    "ptmi_frame_tile_skippable": (_i, [_vp, _i, _i, _i, _i]),
+    "ptmi_frame_pixel_tile_skippable": (_i, [_vp, _i, _i, _i, _i]),
+    "ptmi_frame_skip_lists": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ptmi_conv3x3_wino4p_fwd_list": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "ptmi_frame_fill": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ptmi_conv3x3_wino4_wgrad_fits": (_i, [_i, _i]),
     "ptmi_conv3x3_wino4_wgrad_ws_floats": (_i64, [_i, _i, _i, _i, _i]),
     "ptmi_conv3x3_wino4_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -77,7 +77,10 @@ static_assert(x_free_slot(14) + 3 < XFMA0 && x_valu_before(XHAND) == 72, "wino4p
 // DYN: the dynamic tile schedule (sched != nullptr).  Two instantiations: the schedule's scalar state (queue, pending draw, ids)
 // costs the chunk loop 2.6 % through SGPR pressure (48 more scalar instructions per chunk pair between the MFMAs: measured on the
 // same box against the round-5 kernel, profiles/r06_wino4_static_vs_dynamic.txt), which a single-GPU run need not pay
-template <bool DYN>
+// LIST (static schedule only): the launch walks a LIST of pixel tiles instead of all of them -- nPix is the list's length and
+// `sched` points to the list (ascending pixel-tile numbers of the full walk); everything else, the tile's arithmetic included, is
+// the code of the plain static kernel.  The tiles left out are written by ptmi_frame_fill (frame_skip.hip).
+template <bool DYN, bool LIST = false>
 __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
     const float* __restrict__ x, const float* __restrict__ wpk, const float* __restrict__ bias,
     const float* __restrict__ mref, float* __restrict__ y, int N, int Cin, int Cout, int H, int W, int nChunks, int epi,
@@ -134,10 +137,16 @@ __global__ __launch_bounds__(XNT, 1) void conv3x3_wino4p_kernel(
             const int slot = vid >> 3;
             cot = slot % coTiles;
             pix = (slot / coTiles) * 8 + (vid & 7);
+            if constexpr (LIST) {                                    // (list slot -> pixel tile: one wave-uniform load per decode)
+                const bool ok = pix < nPix;
+                pix = ok ? __builtin_amdgcn_readfirstlane(sched[pix]) : 0;
+                return ok;
+            }
             return pix < nPix;
         }
         cot = vid % coTiles;
         pix = vid / coTiles;
+        if constexpr (LIST) pix = __builtin_amdgcn_readfirstlane(sched[pix]);
         return true;
     };
 
@@ -861,6 +870,40 @@ int ptmi_conv3x3_wino4p_fwd_sched(const float* x, const float* wp, const float* 
 {
     return x_fwd_sched("conv3x3_wino4p_fwd", conv3x3_wino4p_kernel<true>, conv3x3_wino4p_kernel<false>, x, wp, bias, mask_ref, y, n, cin, cout,
                        h, w, epilogue, sched, s);
+}
+
+// The static walk over a list of pixel tiles: pix_list (device memory, n_list ascending pixel-tile numbers of the full walk of
+// this shape, e.g. the `keep` list of ptmi_frame_skip_lists) takes the place of 0 .. nPix - 1.  Outputs of tiles that are not in the
+// list are not written.
+int ptmi_conv3x3_wino4p_fwd_list(const float* x, const float* wp, const float* bias, const float* mask_ref, float* y, int n,
+                                int cin, int cout, int h, int w, int epilogue, const int32_t* pix_list, int n_list, ptmi_stream_t s)
+{
+    const char* name = "conv3x3_wino4p_fwd_list";
+    PTMI_CHECK_ARG(x && wp && y && n > 0 && cin > 0 && cout > 0 && h > 0 && w > 0, "%s: bad args", name);
+    PTMI_CHECK_ARG(epilogue >= 0 && epilogue <= 4, "%s: bad epilogue %d", name, epilogue);
+    PTMI_CHECK_ARG(!(cin & 7), "%s: cin %d is not a multiple of 8", name, cin);
+    PTMI_CHECK_ARG(x_fwd_fits(cin, cout, h, w), "%s: image too large for 32-bit buffer offsets (n=%d cin=%d cout=%d h=%d w=%d)",
+                   name, n, cin, cout, h, w);
+    PTMI_CHECK_ARG(bias || (epilogue > 1 && epilogue != 4), "%s: bias required for epilogue %d", name, epilogue);
+    PTMI_CHECK_ARG(epilogue != 3 || mask_ref, "%s: mask_ref required for epilogue 3", name);
+    const int bands = cdiv(h, XTH), coTiles = cdiv(cout, XBM), nChunks = cin / XKC;
+    const int period = (w + 1 + 3) & ~3;
+    const int64_t nPixFull = cdiv64((int64_t)n * bands * period, XTW);
+    PTMI_CHECK_ARG(nPixFull * XTW < (1ll << 31), "%s: too many tiles", name);
+    PTMI_CHECK_ARG(n_list >= 0 && n_list <= nPixFull, "%s: list of %d pixel tiles, the shape has %lld", name, n_list, (long long)nPixFull);
+    if (n_list == 0) return 0;
+    PTMI_CHECK_ARG(pix_list, "%s: bad args", name);
+    const int64_t nPix = n_list;
+    const int colocate = coTiles <= 4;
+    const int64_t nWg = colocate ? cdiv64(nPix, 8) * 8 * coTiles : nPix * coTiles;
+    PTMI_CHECK_ARG(nWg < (1ll << 31) - 4096, "%s: too many tiles", name);
+    const int cus = ptmi_device_cus();
+    const int64_t grid = nWg < (cus / 8) * 8 ? nWg : (cus / 8) * 8;
+    hipLaunchKernelGGL((conv3x3_wino4p_kernel<false, true>), dim3((unsigned)grid), dim3(XNT), 0, (hipStream_t)s, x, wp, bias, mask_ref, y,
+                       n, cin, cout, h, w, nChunks, epilogue, coTiles, bands, period, (int)nPix, colocate, (int)nWg,
+                       (int*)const_cast<int32_t*>(pix_list));
+    PTMI_LAUNCH_CHECK(name);
+    return 0;
 }
 
 int ptmi_conv3x3_wino4p_fwd(const float* x, const float* wp, const float* bias, const float* mask_ref, float* y, int n,

@@ -157,6 +157,7 @@ class PTrainer:
         images = [rec["image"].to(dev, non_blocking=True) for rec in data]
         ratios = [self._ratio_fn() for _ in data]
         canvases, offsets = ops.shrink_paste_batch(images, ratios, self._mean_int)
+        geometry = [ops.shrink_paste_geometry(int(im.shape[-2]), int(im.shape[-1]), r) for im, r in zip(images, ratios)]
         # boxes of the whole list: ONE multiply and ONE add over the concatenation (per element exactly the reference's fp32
         # `*= ratio` followed by `+= x1` / `+= y1`; a clone + five in-place launches per record were 6 n tiny launches)
         box_fields = [(i, k, v.tensor) for i, rec in enumerate(data) for k, v in rec["instances"].get_fields().items()
@@ -182,6 +183,8 @@ class PTrainer:
         for i, (rec, canvas) in enumerate(zip(data, canvases)):
             new = dict(rec)
             new["image"] = canvas
+            dh, dw, x1, y1 = geometry[i]
+            new["frame"] = (x1, y1, dw, dh, tuple(self._mean_int))   # the pasted rectangle; the rest of the canvas is one colour
             inst = rec["instances"]
             ni = FreeInstances(inst.image_size)
             for k, v in inst.get_fields().items():

@@ -47,22 +47,25 @@ class VGGBlock(nn.Module):
         self.out_channels = in_channels
         self.stride = 2
 
-    def forward(self, x):
+    def forward(self, x, frame=None):
+        """frame: the batch's ops.FrameState at the block's input (shrink-pasted images), advanced layer by layer"""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             params = []
             for i in range(self.num_convs):
                 c = getattr(self, f"conv{i + 1}")
                 params += [c.weight, c.bias]
-            return ops.vgg_block(x, self.pool, params)            # one autograd node, fused backward chain
+            return ops.vgg_block(x, self.pool, params, frame)     # one autograd node, fused backward chain
         fuse_pool = self.pool and not torch.is_grad_enabled()     # frozen block: full-res activation not needed
         for i in range(self.num_convs):
             c = getattr(self, f"conv{i + 1}")
             if fuse_pool and i == self.num_convs - 1:
-                return ops.conv3x3_relu_pool_nograd(x, c.weight, c.bias)
+                return ops.conv3x3_relu_pool_nograd(x, c.weight, c.bias, frame)
             with ops.anomaly_scope(f"conv{i + 1}"):
-                x = ops.conv3x3(x, c.weight, c.bias, True)
+                x = ops.conv3x3(x, c.weight, c.bias, True, frame)
         if self.pool:
+            h, w = x.shape[-2:]
             x = ops.maxpool2x2(x)
+            ops.frame_pool(frame, h, w)
         return x
 
     def freeze(self):
@@ -142,19 +145,22 @@ class VGG(nn.Module):
                     outputs[name] = p8._ToNCHW.apply(t, n, c, h, w)
         return outputs
 
-    def forward(self, x):
+    def forward(self, x, frame=None):
+        """frame: ops.FrameState of a batch with shrink-pasted images (meta_arch.preprocess_image), or None"""
         if ops._native_bf16():
             return self._forward_p8(x)
         outputs = {}
         for name in self._names:
             block = getattr(self, name)[0]
             frozen = not any(p.requires_grad for p in block.parameters())
+            if frame is not None and not frame.alive:
+                frame = None
             with ops.anomaly_scope(name + ".0"):          # (the state-dict path of the block's module: vgg_block{b}.0.conv{k})
                 if frozen and not x.requires_grad:
                     with torch.no_grad():
-                        x = block(x)
+                        x = block(x, frame)
                 else:
-                    x = block(x)
+                    x = block(x, frame)
             if name in self._out_features:
                 outputs[name] = x
         return outputs

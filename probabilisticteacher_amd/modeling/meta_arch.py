@@ -27,6 +27,7 @@ class GuassianGeneralizedRCNN(nn.Module):
         self._mean = [float(v) for v in cfg.MODEL.PIXEL_MEAN]
         self._std = [float(v) for v in cfg.MODEL.PIXEL_STD]
         self.statistics = None
+        self._frame_colours = {}
 
     def enable_statistics(self) -> StatisticsSink:
         """Count what the reference logs beside its losses (modeling/statistics.py): ONE sink, owned here and handed to the
@@ -47,6 +48,25 @@ class GuassianGeneralizedRCNN(nn.Module):
         imgs = [x["image"].to(self.device, non_blocking=True) for x in batched_inputs]
         sizes = [(int(im.shape[-2]), int(im.shape[-1])) for im in imgs]
         return ImageList(ops.preprocess_images(imgs, self._mean, self._std), sizes)
+
+    def frame_state(self, batched_inputs: List[dict], images: ImageList):
+        """The ops.FrameState of a batch whose records carry "frame" = (x1, y1, dw, dh, colour) from PTrainer.resize: per image
+        the canvas and the pasted rectangle, and what a frame pixel holds behind preprocess_image -- the normalisation kernel's
+        own output for that colour, a constant of the model.  None: no record has one (weak views, the teacher), or the
+        tile-list launch is off."""
+        if not ops.frame_skip_active():
+            return None
+        frames = [x.get("frame") for x in batched_inputs]
+        colours = {tuple(f[4]) for f in frames if f is not None}
+        rings = ops.frame_rings([None if f is None else f[:4] for f in frames], images.image_sizes)
+        if rings is None or len(colours) != 1:
+            return None
+        colour = colours.pop()
+        pat = self._frame_colours.get(colour)
+        if pat is None:
+            probe = torch.tensor(colour, dtype=torch.uint8).view(3, 1, 1).expand(3, 8, 8).contiguous().to(self.device)
+            pat = self._frame_colours[colour] = ops.preprocess_images([probe], self._mean, self._std)[0, :, :4, :4].contiguous()
+        return ops.FrameState(rings, pat, ("image", colour, tuple(self._mean), tuple(self._std)))
 
     def inference(self, batched_inputs):
         """Eval-mode path (rcnn.py:33-34 -> D2 GeneralizedRCNN.inference + detector_postprocess):
@@ -83,7 +103,7 @@ class GuassianGeneralizedRCNN(nn.Module):
         # (anomaly mode: the shared backbone + RPN-head pass reports as branch "joint", each branch's heads under its own name)
         with ops.anomaly_branch("joint"):
             with ops.anomaly_scope("backbone"):
-                features = self.backbone(images.tensor)
+                features = self.backbone(images.tensor, self.frame_state(list(sup_inputs) + list(unsup_inputs), images))
             feats = [features[f] for f in self.proposal_generator.in_features]
             with ops.anomaly_scope("proposal_generator"):
                 obj, deltas = self.proposal_generator.head_outputs(feats)
@@ -119,7 +139,7 @@ class GuassianGeneralizedRCNN(nn.Module):
         if "instances" in batched_inputs[0]:
             gt_instances = [x["instances"].to(self.device) for x in batched_inputs]
         with ops.anomaly_scope("backbone"):
-            features = self.backbone(images.tensor)
+            features = self.backbone(images.tensor, self.frame_state(batched_inputs, images))
 
         if branch == "supervised":
             with ops.anomaly_scope("proposal_generator"):

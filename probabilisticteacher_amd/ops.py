@@ -541,11 +541,162 @@ def _conv_fwd_call(kind: str, x, wp, bias, mask_ref, y, n, cin, cout, h, w, epil
                   _stream())
 
 
-def conv3x3_raw(x, wp, bias, mask_ref, cout: int, epilogue: int) -> torch.Tensor:
-    """wp = conv3x3_pack(w, mode, epilogue) with the SAME epilogue."""
+# ---------------------------------------------------------------------------- the constant frame of shrink-pasted images
+# PTrainer.resize pastes every strong view, shrunk, into a canvas of one colour: inside that frame every layer's output is a fixed
+# 4x4-periodic pattern.  A FrameState travels with such a batch through the backbone's forward pass: per image the ring where the
+# NEXT layer's input holds the pattern (csrc/frame_skip.h), and the pattern itself.  A routed layer then runs the tile-list launch
+# (ptmi_conv3x3_wino4p_fwd_list) over the pixel tiles that hold anything else and ptmi_frame_fill over the rest; the pattern of its
+# output comes out of the layer's own kernel, run on a small probe canvas tiled with the input pattern.
+_FRAME_SKIP = True
+# A layer takes the list launch only if the list drops at least this share of its pixel tiles.  Measured per layer at n = 48
+# (profiles/frame_skip_per_layer.txt): the list kernel costs 0.4 - 1.4 % per tile more than the plain one, and a list that drops
+# 2 - 3 % of conv3_2 / conv3_3 ran 4 - 6 % SLOWER than the plain launch; 7.2 % (conv3_1) was the smallest share that won.
+_FRAME_MIN_SHARE = 0.07
+_FRAME_PROBE_HW = (24, 128)
+_FRAME_CACHE: dict = {}
+
+
+def set_frame_skip(on: bool) -> None:
+    """False: every forward launch walks all of its tiles, whatever rings a batch carries (tests, A/B runs)."""
+    global _FRAME_SKIP
+    _FRAME_SKIP = bool(on)
+
+
+def frame_skip_active() -> bool:
+    """the tile-list launch exists for the static schedule of the fp32 wino4p family only"""
+    return (_FRAME_SKIP and _TILE_SCHEDULE == "static" and _WINO4_FAMILY == "wino4p" and _CONV_ALGO == "auto" and
+            _OPERAND_ROUNDING is None)
+
+
+class FrameState:
+    """rings: CPU int32 (n, 8) -- per image outer / inner rectangle in the resolution of the next layer's input (outer x1 <= x0:
+    no ring); pattern: device (C, 4, 4) -- what that input holds inside the rings, indexed [c][y & 3][x & 3]; key: a hashable
+    identity of the pattern (None: not cacheable, it depends on trainable parameters)."""
+
+    def __init__(self, rings: torch.Tensor, pattern: torch.Tensor, key=None):
+        self.rings = rings.to(torch.int32).contiguous()
+        self.pattern = pattern
+        self.key = key
+        self.alive = True
+        self._lists = None
+
+    def lists(self, n: int, h: int, w: int, device):
+        """(device int32 buffer [rings | keep | skip], n_keep, n_skip) for an (n, *, h, w) input: built on the host from the
+        rings, uploaded from pinned memory on the current stream -- no round trip, no synchronisation"""
+        if self._lists is not None and self._lists[0] == (n, h, w):
+            return self._lists[1:]
+        lib = _lib.load()
+        n_pix = int(lib.ptmi_frame_pixel_tiles(n, h, w))
+        host = torch.empty(n * 8 + n_pix, dtype=torch.int32).pin_memory()
+        host[:n * 8] = self.rings.reshape(-1)
+        skip = torch.empty(n_pix, dtype=torch.int32)
+        counts = torch.zeros(2, dtype=torch.int32)
+        _lib.call("ptmi_frame_skip_lists", ctypes.c_void_p(self.rings.data_ptr()), n, h, w,
+                  ctypes.c_void_p(host.data_ptr() + 4 * n * 8), ctypes.c_void_p(skip.data_ptr()), ctypes.c_void_p(counts.data_ptr()))
+        nk, ns = int(counts[0]), int(counts[1])
+        if ns:
+            host[n * 8 + nk:] = skip[:ns]
+        buf = host.to(device, non_blocking=True) if ns else None
+        self._lists = ((n, h, w), buf, nk, ns)
+        return self._lists[1:]
+
+    def share(self, n: int, h: int, w: int, device) -> float:
+        _, nk, ns = self.lists(n, h, w, device)
+        return ns / float(max(nk + ns, 1))
+
+    def advance(self, op: int, h: int, w: int, pattern: torch.Tensor, key=None) -> None:
+        """the state behind a layer with an h x w input: op 0 = conv3x3 by a direct kernel, 1 = max pool 2x2, 2 = conv3x3 by the
+        F(4x4, 3x3) kernels (whole tiles only: ptmi_frame_ring_next)"""
+        nxt = torch.empty_like(self.rings)
+        _lib.call("ptmi_frame_ring_next", ctypes.c_void_p(self.rings.data_ptr()), ctypes.c_void_p(nxt.data_ptr()),
+                  int(self.rings.shape[0]), op, int(h), int(w))
+        self.rings, self.pattern, self.key, self._lists = nxt, pattern, key, None
+
+
+def frame_rings(frames: Sequence[Optional[Tuple[int, int, int, int]]], sizes: Sequence[Tuple[int, int]]) -> Optional[torch.Tensor]:
+    """per image (x1, y1, dw, dh) of PTrainer.resize (None: not a shrink-pasted image) and its (h, w) -> rings at image resolution,
+    or None if no image has one"""
+    if not any(f is not None for f in frames):
+        return None
+    rows = []
+    for f, (h, w) in zip(frames, sizes):
+        rows.append([0] * 8 if f is None else [0, 0, int(w), int(h), int(f[0]), int(f[1]), int(f[0]) + int(f[2]), int(f[1]) + int(f[3])])
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+def _frame_tile_pattern(pattern: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    return pattern.repeat(1, h // 4, w // 4).unsqueeze(0).contiguous()
+
+
+def _frame_probe(run, frame: FrameState, cache_key, pooled: bool) -> Tuple[torch.Tensor, object]:
+    """The pattern of a layer's output from the layer's own kernel: run(probe canvas) -> its output on a canvas tiled with the input
+    pattern; one interior, tile-aligned 4x4 block per channel.  cache_key (frozen layers: parameter versions, kernel family) makes the
+    result a constant of the model as long as the input pattern is one too."""
+    key = None if (cache_key is None or frame.key is None) else (frame.key, cache_key, pooled)
+    if key is not None and key in _FRAME_CACHE:
+        return _FRAME_CACHE[key], key
+    ph, pw = _FRAME_PROBE_HW
+    with _prof("frame_probe"):
+        y = run(_frame_tile_pattern(frame.pattern, ph, pw))
+        pat = (y[0, :, 4:8, 4:8] if pooled else y[0, :, 8:12, 8:12]).contiguous()
+    if key is not None:
+        if len(_FRAME_CACHE) >= 64:          # (parameters reloaded many times over: start again)
+            _FRAME_CACHE.clear()
+        _FRAME_CACHE[key] = pat
+    return pat, key
+
+
+class _param_key:
+    """identity of frozen parameters as a cache key: storage, version counter and shape when the key was made.  The key holds the
+    tensors, so a cached entry's storage cannot be freed and handed to other parameters."""
+
+    def __init__(self, *params):
+        self.params = params
+        self.id = tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in params)
+
+    def __hash__(self):
+        return hash(self.id)
+
+    def __eq__(self, other):
+        return isinstance(other, _param_key) and self.id == other.id
+
+
+def frame_pool(frame: Optional[FrameState], h: int, w: int) -> None:
+    """a separate 2x2 max pool of an h x w map behind the layer: the pooled pattern is the pool kernel's output on the tiled pattern"""
+    if frame is None or not frame.alive:
+        return
+    c = frame.pattern.shape[0]
+    src = _frame_tile_pattern(frame.pattern, 8, 8)
+    out = torch.empty((1, c, 4, 4), dtype=F32, device=src.device)
+    _lib.call("ptmi_maxpool2x2_fwd", _ptr(src), _ptr(out), c, 8, 8, _stream())
+    frame.advance(1, h, w, out[0], None if frame.key is None else (frame.key, "pool"))
+
+
+def _conv_fwd_frame(kind: str, x, wp, bias, y, n, cin, cout, h, w, epilogue, frame: FrameState, pat_out) -> bool:
+    """the list launch + fill, if the layer is routed to them and the list drops a worthwhile share; False: nothing launched"""
+    if kind != "wino4" or not frame_skip_active() or epilogue not in (1, 4):
+        return False
+    buf, nk, ns = frame.lists(n, h, w, x.device)
+    if ns < _FRAME_MIN_SHARE * (nk + ns) or ns == 0:
+        return False
+    base = buf.data_ptr()
+    _lib.call("ptmi_conv3x3_wino4p_fwd_list", _ptr(x), _ptr(wp), _ptr(bias), None, _ptr(y), n, cin, cout, h, w, epilogue,
+              ctypes.c_void_p(base + 4 * n * 8), nk, _stream())
+    _lib.call("ptmi_frame_fill", ctypes.c_void_p(base + 4 * (n * 8 + nk)), ns, ctypes.c_void_p(base), _ptr(pat_out), _ptr(y), n, cout,
+              h, w, int(epilogue == 4), _stream())
+    return True
+
+
+def conv3x3_raw(x, wp, bias, mask_ref, cout: int, epilogue: int, frame: Optional[FrameState] = None, frame_key=None) -> torch.Tensor:
+    """wp = conv3x3_pack(w, mode, epilogue) with the SAME epilogue.  frame: the batch's FrameState at this layer's input (forward
+    layers with epilogue 1 only); it is advanced to the layer's output.  frame_key: identity of (weights, bias) if they are frozen."""
     _no_native_bf16("ops.conv3x3_raw")
     _chk(x, name="conv input")
     n, cin, h, w = x.shape
+    if frame is not None and frame.alive and frame_skip_active() and epilogue == 1:
+        return _conv3x3_raw_frame(x, wp, bias, cout, frame, frame_key)
+    if frame is not None:
+        frame.alive = False
     y = torch.empty((n, cout, h, w), dtype=F32, device=x.device)
     nbytes = 4.0 * (n * h * w * (cin + cout * (2 if epilogue == 3 else 1)) + 9 * cin * cout)
     kind = _conv_kind(cin, cout, (h, w))
@@ -559,10 +710,62 @@ def conv3x3_raw(x, wp, bias, mask_ref, cout: int, epilogue: int) -> torch.Tensor
     return y
 
 
-def conv3x3_relu_pool_nograd(x, weight, bias) -> torch.Tensor:
-    """conv3x3 + bias + ReLU + MaxPool(2,2) in ONE kernel (epilogue 4); inference-only (no autograd state)."""
+def _frame_layer(x, wp, bias, y, cout: int, epilogue: int, frame: FrameState, frame_key, flops, nbytes) -> None:
+    """one forward layer of a batch that carries a FrameState: the output pattern from a probe launch of the layer's own entry
+    point (same packed weights, bias and epilogue), then the list launch + fill or the plain launch; advances the state"""
+    n, cin, h, w = x.shape
+    kind = _conv_kind(cin, cout, (h, w))
+    pooled = epilogue == 4
+    ph, pw = _FRAME_PROBE_HW
+    # the layer's kernel must be one whose outputs are known to repeat bit for bit: the F(4x4, 3x3) family (tile by tile) or the
+    # 3-channel stem kernel (pixel by pixel); and the probe must run the same one
+    if not (kind == "wino4" or (kind == "mfma" and cin < 8)) or _conv_kind(cin, cout, (ph, pw)) != kind:
+        frame.alive = False
+        with _prof("conv3x3_" + kind, flops, nbytes, _conv_issued(kind, n, cin, cout, h, w)):
+            _conv_fwd_call(kind, x, wp, bias, None, y, n, cin, cout, h, w, epilogue)
+        return
+
+    def run(canvas):
+        out = torch.empty((1, cout, ph // 2, pw // 2) if pooled else (1, cout, ph, pw), dtype=F32, device=x.device)
+        _conv_fwd_call(kind, canvas, wp, bias, None, out, 1, cin, cout, ph, pw, epilogue)
+        return out
+
+    pat, key = _frame_probe(run, frame, None if frame_key is None else (frame_key, kind, _WINO4_FAMILY), pooled)
+    with _prof("conv3x3_" + kind, flops, nbytes, _conv_issued(kind, n, cin, cout, h, w)):
+        if not _conv_fwd_frame(kind, x, wp, bias, y, n, cin, cout, h, w, epilogue, frame, pat):
+            _conv_fwd_call(kind, x, wp, bias, None, y, n, cin, cout, h, w, epilogue)
+    op = 2 if kind == "wino4" else 0
+    if pooled:        # the pattern is the pooled one already; the rings pass the convolution, then the pool
+        frame.advance(op, h, w, pat, None)
+        frame.advance(1, h, w, pat, key)
+        h, w = h // 2, w // 2
+    else:
+        frame.advance(op, h, w, pat, key)
+    # the chain ends at the first layer whose input would not be worth a list launch (rings only shrink, tiles only grow)
+    if h < 8 or w < 8 or frame.share(n, h, w, x.device) < _FRAME_MIN_SHARE:
+        frame.alive = False
+
+
+def _conv3x3_raw_frame(x, wp, bias, cout: int, frame: FrameState, frame_key) -> torch.Tensor:
+    n, cin, h, w = x.shape
+    y = torch.empty((n, cout, h, w), dtype=F32, device=x.device)
+    kind = _conv_kind(cin, cout, (h, w))
+    want = getattr(_lib.load(), _conv_abi(kind) + "_packed_floats")(cin, cout)
+    if wp.numel() != want:
+        raise _lib.PtmiError(f"conv3x3_raw: packed weights have {wp.numel()} floats, the {kind} kernel this {h}x{w} map is "
+                             f"routed to takes {want} (pass hw=(H, W) to conv3x3_pack)")
+    _frame_layer(x, wp, bias, y, cout, 1, frame, frame_key, 2.0 * 9 * cin * cout * h * w * n,
+                 4.0 * (n * h * w * (cin + cout) + 9 * cin * cout))
+    return y
+
+
+def conv3x3_relu_pool_nograd(x, weight, bias, frame: Optional[FrameState] = None) -> torch.Tensor:
+    """conv3x3 + bias + ReLU + MaxPool(2,2) in ONE kernel (epilogue 4); inference-only (no autograd state).  frame: as conv3x3_raw
+    (the layer's parameters have no backward pass here: they count as frozen)."""
     if _native_bf16():
         from . import p8
+        if frame is not None:
+            frame.alive = False
         return p8.conv3x3_relu_pool_nograd_nchw(_chk(x.contiguous(), name="conv input"), weight, bias)
     x = _chk(_rnd(x).contiguous(), name="conv input")
     n, cin, h, w = x.shape
@@ -570,8 +773,13 @@ def conv3x3_relu_pool_nograd(x, weight, bias) -> torch.Tensor:
     wp = conv3x3_pack(_chk(_rnd(weight).contiguous()), 0, 4, (h, w))
     y = torch.empty((n, cout, h // 2, w // 2), dtype=F32, device=x.device)
     kind = _conv_kind(cin, cout, (h, w))
-    with _prof("conv3x3_" + kind, 2.0 * 9 * cin * cout * h * w * n, 4.0 * (n * h * w * (cin + cout / 4.0) + 9 * cin * cout),
-               _conv_issued(kind, n, cin, cout, h, w)):
+    flops, nbytes = 2.0 * 9 * cin * cout * h * w * n, 4.0 * (n * h * w * (cin + cout / 4.0) + 9 * cin * cout)
+    if frame is not None and frame.alive and frame_skip_active():
+        _frame_layer(x, wp, _chk(bias.contiguous()), y, cout, 4, frame, _param_key(weight, bias), flops, nbytes)
+        return y
+    if frame is not None:
+        frame.alive = False
+    with _prof("conv3x3_" + kind, flops, nbytes, _conv_issued(kind, n, cin, cout, h, w)):
         _conv_fwd_call(kind, x, wp, _chk(bias.contiguous()), None, y, n, cin, cout, h, w, 4)
     return _rnd_stored(y)
 
@@ -589,12 +797,13 @@ class _Conv3x3(torch.autograd.Function):
     """conv3x3 s1 p1 + bias (+ ReLU).  Replaces Conv2d + F.relu_ (vgg.py:45-53,66-69)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu: bool):
+    def forward(ctx, x, weight, bias, relu: bool, frame=None):
+        frame_key = None if (frame is None or weight.requires_grad or bias.requires_grad) else _param_key(weight, bias)
         x = _chk(_rnd(x).contiguous(), name="conv input")
         weight = _chk(_rnd(weight).contiguous(), name="conv weight")
         bias = _chk(bias.contiguous(), name="conv bias")
         wp = conv3x3_pack(weight, 0, 1 if relu else 0, x.shape[-2:])
-        y = _rnd_stored(conv3x3_raw(x, wp, bias, None, weight.shape[0], 1 if relu else 0))
+        y = _rnd_stored(conv3x3_raw(x, wp, bias, None, weight.shape[0], 1 if relu else 0, frame, frame_key))
         ctx.relu = relu
         ctx.save_for_backward(x, weight, y if relu else None)
         if _ANOMALY is not None:
@@ -616,14 +825,17 @@ class _Conv3x3(torch.autograd.Function):
             dx = _rnd_stored(conv3x3_raw(dz, wpd, None, None, cin, 2))
         if _ANOMALY is not None:
             _anomaly_bwd(ctx, "conv3x3", (("dw", dw), ("db", db), ("dx", dx)))
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
-def conv3x3(x, weight, bias, relu: bool = True):
+def conv3x3(x, weight, bias, relu: bool = True, frame: Optional[FrameState] = None):
+    """frame: the batch's FrameState at this layer's input (advanced to its output; dropped on paths that do not serve it)"""
     if _native_bf16():
         from . import p8
+        if frame is not None:
+            frame.alive = False
         return p8.conv3x3_nchw(_chk(x.contiguous(), name="conv input"), weight, bias, relu)
-    return _Conv3x3.apply(x, weight, bias, relu)
+    return _Conv3x3.apply(x, weight, bias, relu, frame)
 
 
 # ============================================================================ max pool
@@ -663,14 +875,15 @@ class _VGGBlock(torch.autograd.Function):
     passes (read dy + read y + write dz per layer) remain inside a block."""
 
     @staticmethod
-    def forward(ctx, x, pool: bool, *wb):
+    def forward(ctx, x, pool: bool, frame, *wb):
         k = len(wb) // 2
         acts = [_chk(x.contiguous(), name="block input")]
         ws = []
         for j in range(k):
+            frame_key = None if (frame is None or wb[2 * j].requires_grad or wb[2 * j + 1].requires_grad) else _param_key(wb[2 * j], wb[2 * j + 1])
             w, b = _chk(wb[2 * j].contiguous()), _chk(wb[2 * j + 1].contiguous())
             ws.append(w)
-            acts.append(conv3x3_raw(acts[-1], conv3x3_pack(w, 0, 1, acts[-1].shape[-2:]), b, None, w.shape[0], 1))
+            acts.append(conv3x3_raw(acts[-1], conv3x3_pack(w, 0, 1, acts[-1].shape[-2:]), b, None, w.shape[0], 1, frame, frame_key))
         out = acts[-1]
         if pool:
             n, c, h, wd = out.shape
@@ -678,6 +891,7 @@ class _VGGBlock(torch.autograd.Function):
             with _prof("maxpool_fwd"):
                 _lib.call("ptmi_maxpool2x2_fwd", _ptr(out), _ptr(pooled), n * c, h, wd, _stream())
             out = pooled
+            frame_pool(frame, h, wd)
         ctx.k, ctx.pool = k, pool
         ctx.save_for_backward(*acts, *ws)
         if _ANOMALY is not None:        # layer granularity: the node covers a whole block
@@ -705,7 +919,7 @@ class _VGGBlock(torch.autograd.Function):
             xin, w = acts[j - 1], ws[j - 1]
             n, cin, h, wd = xin.shape
             cout = w.shape[0]
-            if ctx.needs_input_grad[2 + 2 * (j - 1)] or ctx.needs_input_grad[3 + 2 * (j - 1)]:
+            if ctx.needs_input_grad[3 + 2 * (j - 1)] or ctx.needs_input_grad[4 + 2 * (j - 1)]:      # (x, pool, frame, w1, b1, ...)
                 dw, db = conv3x3_wgrad(xin, dz, cout)
                 grads[2 * (j - 1)], grads[2 * (j - 1) + 1] = dw, db
                 if seen is not None:
@@ -720,19 +934,23 @@ class _VGGBlock(torch.autograd.Function):
                     seen.append(("dx", dx, "conv1"))
         if seen is not None:
             _anomaly_bwd(ctx, "vgg_block", seen)
-        return (dx, None, *grads)
+        return (dx, None, None, *grads)
 
 
-def vgg_block(x, pool: bool, params):
-    """params = [w1, b1, w2, b2, ...]."""
+def vgg_block(x, pool: bool, params, frame: Optional[FrameState] = None):
+    """params = [w1, b1, w2, b2, ...].  frame: as conv3x3."""
     if _native_bf16():
         from . import p8
+        if frame is not None:
+            frame.alive = False
         return p8.vgg_block_nchw(_chk(x.contiguous(), name="block input"), pool, params)
     if _OPERAND_ROUNDING == "bf16_emulate":    # layer by layer: every conv rounds its own operands
+        if frame is not None:
+            frame.alive = False
         for j in range(len(params) // 2):
             x = conv3x3(x, params[2 * j], params[2 * j + 1], True)
         return maxpool2x2(x) if pool else x
-    return _VGGBlock.apply(x, pool, *params)
+    return _VGGBlock.apply(x, pool, frame, *params)
 
 
 # ============================================================================ GEMM family
