@@ -47,14 +47,15 @@ class VGGBlock(nn.Module):
         self.out_channels = in_channels
         self.stride = 2
 
+    def conv_params(self):
+        """[w1, b1, w2, b2, ...]: what ops.vgg_block and p8.block take"""
+        convs = [getattr(self, f"conv{i + 1}") for i in range(self.num_convs)]
+        return [p for c in convs for p in (c.weight, c.bias)]
+
     def forward(self, x, frame=None):
         """frame: the batch's ops.FrameState at the block's input (shrink-pasted images), advanced layer by layer"""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            params = []
-            for i in range(self.num_convs):
-                c = getattr(self, f"conv{i + 1}")
-                params += [c.weight, c.bias]
-            return ops.vgg_block(x, self.pool, params, frame)     # one autograd node, fused backward chain
+            return ops.vgg_block(x, self.pool, self.conv_params(), frame)     # one autograd node, fused backward chain
         fuse_pool = self.pool and not torch.is_grad_enabled()     # frozen block: full-res activation not needed
         for i in range(self.num_convs):
             c = getattr(self, f"conv{i + 1}")
@@ -62,11 +63,7 @@ class VGGBlock(nn.Module):
                 return ops.conv3x3_relu_pool_nograd(x, c.weight, c.bias, frame)
             with ops.anomaly_scope(f"conv{i + 1}"):
                 x = ops.conv3x3(x, c.weight, c.bias, True, frame)
-        if self.pool:
-            h, w = x.shape[-2:]
-            x = ops.maxpool2x2(x)
-            ops.frame_pool(frame, h, w)
-        return x
+        return ops.maxpool2x2(x, frame) if self.pool else x
 
     def freeze(self):
         for p in self.parameters():
@@ -120,10 +117,7 @@ class VGG(nn.Module):
         outputs = {}
         for name in self._names:
             blk = getattr(self, name)[0]
-            params = []
-            for i in range(blk.num_convs):
-                cv = getattr(blk, f"conv{i + 1}")
-                params += [cv.weight, cv.bias]
+            params = blk.conv_params()
             trainable = torch.is_grad_enabled() and any(p.requires_grad for p in params)
             if trainable or t.requires_grad:
                 with ops.anomaly_scope(name + ".0"):

@@ -672,91 +672,79 @@ def frame_pool(frame: Optional[FrameState], h: int, w: int) -> None:
     frame.advance(1, h, w, out[0], None if frame.key is None else (frame.key, "pool"))
 
 
-def _conv_fwd_frame(kind: str, x, wp, bias, y, n, cin, cout, h, w, epilogue, frame: FrameState, pat_out) -> bool:
-    """the list launch + fill, if the layer is routed to them and the list drops a worthwhile share; False: nothing launched"""
-    if kind != "wino4" or not frame_skip_active() or epilogue not in (1, 4):
-        return False
-    buf, nk, ns = frame.lists(n, h, w, x.device)
-    if ns < _FRAME_MIN_SHARE * (nk + ns) or ns == 0:
-        return False
-    base = buf.data_ptr()
-    _lib.call("ptmi_conv3x3_wino4p_fwd_list", _ptr(x), _ptr(wp), _ptr(bias), None, _ptr(y), n, cin, cout, h, w, epilogue,
-              ctypes.c_void_p(base + 4 * n * 8), nk, _stream())
-    _lib.call("ptmi_frame_fill", ctypes.c_void_p(base + 4 * (n * 8 + nk)), ns, ctypes.c_void_p(base), _ptr(pat_out), _ptr(y), n, cout,
-              h, w, int(epilogue == 4), _stream())
-    return True
-
-
-def conv3x3_raw(x, wp, bias, mask_ref, cout: int, epilogue: int, frame: Optional[FrameState] = None, frame_key=None) -> torch.Tensor:
-    """wp = conv3x3_pack(w, mode, epilogue) with the SAME epilogue.  frame: the batch's FrameState at this layer's input (forward
-    layers with epilogue 1 only); it is advanced to the layer's output.  frame_key: identity of (weights, bias) if they are frozen."""
-    _no_native_bf16("ops.conv3x3_raw")
-    _chk(x, name="conv input")
-    n, cin, h, w = x.shape
-    if frame is not None and frame.alive and frame_skip_active() and epilogue == 1:
-        return _conv3x3_raw_frame(x, wp, bias, cout, frame, frame_key)
+def _frame_end(frame: Optional[FrameState]) -> None:
+    """a path that does not serve a FrameState ends its chain: no layer behind it probes or takes the list launch"""
     if frame is not None:
         frame.alive = False
-    y = torch.empty((n, cout, h, w), dtype=F32, device=x.device)
-    nbytes = 4.0 * (n * h * w * (cin + cout * (2 if epilogue == 3 else 1)) + 9 * cin * cout)
-    kind = _conv_kind(cin, cout, (h, w))
-    abi = _conv_abi(kind)
-    want = getattr(_lib.load(), abi + "_packed_floats")(cin, cout)
-    if wp.numel() != want:
-        raise _lib.PtmiError(f"conv3x3_raw: packed weights have {wp.numel()} floats, the {kind} kernel this {h}x{w} map is "
-                             f"routed to takes {want} (pass hw=(H, W) to conv3x3_pack)")
-    with _prof("conv3x3_" + kind, 2.0 * 9 * cin * cout * h * w * n, nbytes, _conv_issued(kind, n, cin, cout, h, w)):
-        _conv_fwd_call(kind, x, wp, bias, mask_ref, y, n, cin, cout, h, w, epilogue)
-    return y
 
 
-def _frame_layer(x, wp, bias, y, cout: int, epilogue: int, frame: FrameState, frame_key, flops, nbytes) -> None:
-    """one forward layer of a batch that carries a FrameState: the output pattern from a probe launch of the layer's own entry
-    point (same packed weights, bias and epilogue), then the list launch + fill or the plain launch; advances the state"""
+def _frame_key(frame: Optional[FrameState], weight, bias):
+    """cache identity of a layer's parameters for _frame_probe: None without a frame, or when either is trainable (probe every step)"""
+    return None if (frame is None or weight.requires_grad or bias.requires_grad) else _param_key(weight, bias)
+
+
+def _conv3x3_launch(x, wp, bias, mask_ref, cout: int, epilogue: int, frame: Optional[FrameState] = None, frame_key=None) -> torch.Tensor:
+    """The one launch of an fp32 3x3 layer, forward (epilogue 0 / 1 / 4) or dgrad (2 / 3): output, route, pack check, work figures,
+    profile bracket.  A live FrameState is served on the forward epilogues 1 and 4: the output pattern from a probe launch of the
+    layer's own entry point (same packed weights, bias and epilogue), then the list launch + fill or the plain launch, then the
+    state moves to the layer's output.  Every other path ends it."""
     n, cin, h, w = x.shape
-    kind = _conv_kind(cin, cout, (h, w))
     pooled = epilogue == 4
-    ph, pw = _FRAME_PROBE_HW
-    # the layer's kernel must be one whose outputs are known to repeat bit for bit: the F(4x4, 3x3) family (tile by tile) or the
-    # 3-channel stem kernel (pixel by pixel); and the probe must run the same one
-    if not (kind == "wino4" or (kind == "mfma" and cin < 8)) or _conv_kind(cin, cout, (ph, pw)) != kind:
-        frame.alive = False
-        with _prof("conv3x3_" + kind, flops, nbytes, _conv_issued(kind, n, cin, cout, h, w)):
-            _conv_fwd_call(kind, x, wp, bias, None, y, n, cin, cout, h, w, epilogue)
-        return
-
-    def run(canvas):
-        out = torch.empty((1, cout, ph // 2, pw // 2) if pooled else (1, cout, ph, pw), dtype=F32, device=x.device)
-        _conv_fwd_call(kind, canvas, wp, bias, None, out, 1, cin, cout, ph, pw, epilogue)
-        return out
-
-    pat, key = _frame_probe(run, frame, None if frame_key is None else (frame_key, kind, _WINO4_FAMILY), pooled)
-    with _prof("conv3x3_" + kind, flops, nbytes, _conv_issued(kind, n, cin, cout, h, w)):
-        if not _conv_fwd_frame(kind, x, wp, bias, y, n, cin, cout, h, w, epilogue, frame, pat):
-            _conv_fwd_call(kind, x, wp, bias, None, y, n, cin, cout, h, w, epilogue)
-    op = 2 if kind == "wino4" else 0
-    if pooled:        # the pattern is the pooled one already; the rings pass the convolution, then the pool
-        frame.advance(op, h, w, pat, None)
-        frame.advance(1, h, w, pat, key)
-        h, w = h // 2, w // 2
-    else:
-        frame.advance(op, h, w, pat, key)
-    # the chain ends at the first layer whose input would not be worth a list launch (rings only shrink, tiles only grow)
-    if h < 8 or w < 8 or frame.share(n, h, w, x.device) < _FRAME_MIN_SHARE:
-        frame.alive = False
-
-
-def _conv3x3_raw_frame(x, wp, bias, cout: int, frame: FrameState, frame_key) -> torch.Tensor:
-    n, cin, h, w = x.shape
-    y = torch.empty((n, cout, h, w), dtype=F32, device=x.device)
+    y = torch.empty((n, cout, h // 2, w // 2) if pooled else (n, cout, h, w), dtype=F32, device=x.device)
     kind = _conv_kind(cin, cout, (h, w))
     want = getattr(_lib.load(), _conv_abi(kind) + "_packed_floats")(cin, cout)
     if wp.numel() != want:
         raise _lib.PtmiError(f"conv3x3_raw: packed weights have {wp.numel()} floats, the {kind} kernel this {h}x{w} map is "
                              f"routed to takes {want} (pass hw=(H, W) to conv3x3_pack)")
-    _frame_layer(x, wp, bias, y, cout, 1, frame, frame_key, 2.0 * 9 * cin * cout * h * w * n,
-                 4.0 * (n * h * w * (cin + cout) + 9 * cin * cout))
+    flops = 2.0 * 9 * cin * cout * h * w * n
+    nbytes = 4.0 * (n * h * w * (cin + cout * {3: 2, 4: 0.25}.get(epilogue, 1)) + 9 * cin * cout)
+    ph, pw = _FRAME_PROBE_HW
+    # a frame is served by a kernel whose outputs are known to repeat bit for bit: the F(4x4, 3x3) family (tile by tile) or the
+    # 3-channel stem kernel (pixel by pixel); and the probe must run the same one
+    served = (frame is not None and frame.alive and frame_skip_active() and epilogue in (1, 4) and
+              (kind == "wino4" or (kind == "mfma" and cin < 8)) and _conv_kind(cin, cout, (ph, pw)) == kind)
+    base = None
+    if served:
+        def run(canvas):
+            out = torch.empty((1, cout, ph // 2, pw // 2) if pooled else (1, cout, ph, pw), dtype=F32, device=x.device)
+            _conv_fwd_call(kind, canvas, wp, bias, None, out, 1, cin, cout, ph, pw, epilogue)
+            return out
+
+        pat, key = _frame_probe(run, frame, None if frame_key is None else (frame_key, kind, _WINO4_FAMILY), pooled)
+        if kind == "wino4":       # the list launch + fill, if the list drops a worthwhile share of the pixel tiles
+            buf, nk, ns = frame.lists(n, h, w, x.device)
+            if ns > 0 and ns >= _FRAME_MIN_SHARE * (nk + ns):
+                base = buf.data_ptr()
+    else:
+        _frame_end(frame)
+    with _prof("conv3x3_" + kind, flops, nbytes, _conv_issued(kind, n, cin, cout, h, w)):
+        if base is not None:
+            _lib.call("ptmi_conv3x3_wino4p_fwd_list", _ptr(x), _ptr(wp), _ptr(bias), None, _ptr(y), n, cin, cout, h, w, epilogue,
+                      ctypes.c_void_p(base + 4 * n * 8), nk, _stream())
+            _lib.call("ptmi_frame_fill", ctypes.c_void_p(base + 4 * (n * 8 + nk)), ns, ctypes.c_void_p(base), _ptr(pat), _ptr(y), n,
+                      cout, h, w, int(pooled), _stream())
+        else:
+            _conv_fwd_call(kind, x, wp, bias, mask_ref, y, n, cin, cout, h, w, epilogue)
+    if served:
+        op = 2 if kind == "wino4" else 0
+        if pooled:        # the pattern is the pooled one already; the rings pass the convolution, then the pool
+            frame.advance(op, h, w, pat, None)
+            frame.advance(1, h, w, pat, key)
+            h, w = h // 2, w // 2
+        else:
+            frame.advance(op, h, w, pat, key)
+        # the chain ends at the first layer whose input would not be worth a list launch (rings only shrink, tiles only grow)
+        if h < 8 or w < 8 or frame.share(n, h, w, x.device) < _FRAME_MIN_SHARE:
+            _frame_end(frame)
     return y
+
+
+def conv3x3_raw(x, wp, bias, mask_ref, cout: int, epilogue: int, frame: Optional[FrameState] = None, frame_key=None) -> torch.Tensor:
+    """wp = conv3x3_pack(w, mode, epilogue) with the SAME epilogue.  frame: the batch's FrameState at this layer's input; a forward
+    layer with a ReLU (epilogue 1; the pooled epilogue 4 comes through conv3x3_relu_pool_nograd) advances it to the layer's output,
+    every other epilogue ends it.  frame_key: identity of (weights, bias) if they are frozen."""
+    _no_native_bf16("ops.conv3x3_raw")
+    return _conv3x3_launch(_chk(x, name="conv input"), wp, bias, mask_ref, cout, epilogue, frame, frame_key)
 
 
 def conv3x3_relu_pool_nograd(x, weight, bias, frame: Optional[FrameState] = None) -> torch.Tensor:
@@ -764,24 +752,12 @@ def conv3x3_relu_pool_nograd(x, weight, bias, frame: Optional[FrameState] = None
     (the layer's parameters have no backward pass here: they count as frozen)."""
     if _native_bf16():
         from . import p8
-        if frame is not None:
-            frame.alive = False
+        _frame_end(frame)
         return p8.conv3x3_relu_pool_nograd_nchw(_chk(x.contiguous(), name="conv input"), weight, bias)
     x = _chk(_rnd(x).contiguous(), name="conv input")
-    n, cin, h, w = x.shape
-    cout = weight.shape[0]
-    wp = conv3x3_pack(_chk(_rnd(weight).contiguous()), 0, 4, (h, w))
-    y = torch.empty((n, cout, h // 2, w // 2), dtype=F32, device=x.device)
-    kind = _conv_kind(cin, cout, (h, w))
-    flops, nbytes = 2.0 * 9 * cin * cout * h * w * n, 4.0 * (n * h * w * (cin + cout / 4.0) + 9 * cin * cout)
-    if frame is not None and frame.alive and frame_skip_active():
-        _frame_layer(x, wp, _chk(bias.contiguous()), y, cout, 4, frame, _param_key(weight, bias), flops, nbytes)
-        return y
-    if frame is not None:
-        frame.alive = False
-    with _prof("conv3x3_" + kind, flops, nbytes, _conv_issued(kind, n, cin, cout, h, w)):
-        _conv_fwd_call(kind, x, wp, _chk(bias.contiguous()), None, y, n, cin, cout, h, w, 4)
-    return _rnd_stored(y)
+    wp = conv3x3_pack(_chk(_rnd(weight).contiguous()), 0, 4, x.shape[-2:])
+    frame_key = _frame_key(frame, weight.detach(), bias.detach())       # (detached: frozen as far as this call goes)
+    return _rnd_stored(_conv3x3_launch(x, wp, _chk(bias.contiguous()), None, weight.shape[0], 4, frame, frame_key))
 
 
 def relu_bwd(dy: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -798,7 +774,7 @@ class _Conv3x3(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu: bool, frame=None):
-        frame_key = None if (frame is None or weight.requires_grad or bias.requires_grad) else _param_key(weight, bias)
+        frame_key = _frame_key(frame, weight, bias)
         x = _chk(_rnd(x).contiguous(), name="conv input")
         weight = _chk(_rnd(weight).contiguous(), name="conv weight")
         bias = _chk(bias.contiguous(), name="conv bias")
@@ -832,21 +808,27 @@ def conv3x3(x, weight, bias, relu: bool = True, frame: Optional[FrameState] = No
     """frame: the batch's FrameState at this layer's input (advanced to its output; dropped on paths that do not serve it)"""
     if _native_bf16():
         from . import p8
-        if frame is not None:
-            frame.alive = False
+        _frame_end(frame)
         return p8.conv3x3_nchw(_chk(x.contiguous(), name="conv input"), weight, bias, relu)
     return _Conv3x3.apply(x, weight, bias, relu, frame)
 
 
 # ============================================================================ max pool
+def _maxpool2x2_fwd(x, frame: Optional[FrameState] = None) -> torch.Tensor:
+    """2x2 max pool of a checked map; a live FrameState passes the pool with it"""
+    n, c, h, w = x.shape
+    y = torch.empty((n, c, h // 2, w // 2), dtype=F32, device=x.device)
+    with _prof("maxpool_fwd"):
+        _lib.call("ptmi_maxpool2x2_fwd", _ptr(x), _ptr(y), n * c, h, w, _stream())
+    frame_pool(frame, h, w)
+    return y
+
+
 class _MaxPool2x2(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, frame=None):
         x = _chk(x.contiguous(), name="pool input")
-        n, c, h, w = x.shape
-        y = torch.empty((n, c, h // 2, w // 2), dtype=F32, device=x.device)
-        with _prof("maxpool_fwd"):
-            _lib.call("ptmi_maxpool2x2_fwd", _ptr(x), _ptr(y), n * c, h, w, _stream())
+        y = _maxpool2x2_fwd(x, frame)
         ctx.save_for_backward(x)
         if _ANOMALY is not None:
             _anomaly_fwd(ctx, "maxpool2x2", (("y", y),))
@@ -860,11 +842,12 @@ class _MaxPool2x2(torch.autograd.Function):
         _lib.call("ptmi_maxpool2x2_bwd", _ptr(x), _ptr(_chk(dy.contiguous())), _ptr(dx), n * c, h, w, 0, _stream())
         if _ANOMALY is not None:
             _anomaly_bwd(ctx, "maxpool2x2", (("dx", dx),))
-        return dx
+        return dx, None
 
 
-def maxpool2x2(x):
-    return _MaxPool2x2.apply(x)
+def maxpool2x2(x, frame: Optional[FrameState] = None):
+    """frame: as conv3x3 (the state passes the pool with the map)"""
+    return _MaxPool2x2.apply(x, frame)
 
 
 class _VGGBlock(torch.autograd.Function):
@@ -880,18 +863,11 @@ class _VGGBlock(torch.autograd.Function):
         acts = [_chk(x.contiguous(), name="block input")]
         ws = []
         for j in range(k):
-            frame_key = None if (frame is None or wb[2 * j].requires_grad or wb[2 * j + 1].requires_grad) else _param_key(wb[2 * j], wb[2 * j + 1])
             w, b = _chk(wb[2 * j].contiguous()), _chk(wb[2 * j + 1].contiguous())
             ws.append(w)
-            acts.append(conv3x3_raw(acts[-1], conv3x3_pack(w, 0, 1, acts[-1].shape[-2:]), b, None, w.shape[0], 1, frame, frame_key))
-        out = acts[-1]
-        if pool:
-            n, c, h, wd = out.shape
-            pooled = torch.empty((n, c, h // 2, wd // 2), dtype=F32, device=out.device)
-            with _prof("maxpool_fwd"):
-                _lib.call("ptmi_maxpool2x2_fwd", _ptr(out), _ptr(pooled), n * c, h, wd, _stream())
-            out = pooled
-            frame_pool(frame, h, wd)
+            acts.append(conv3x3_raw(acts[-1], conv3x3_pack(w, 0, 1, acts[-1].shape[-2:]), b, None, w.shape[0], 1, frame,
+                                    _frame_key(frame, wb[2 * j], wb[2 * j + 1])))
+        out = _maxpool2x2_fwd(acts[-1], frame) if pool else acts[-1]
         ctx.k, ctx.pool = k, pool
         ctx.save_for_backward(*acts, *ws)
         if _ANOMALY is not None:        # layer granularity: the node covers a whole block
@@ -941,12 +917,10 @@ def vgg_block(x, pool: bool, params, frame: Optional[FrameState] = None):
     """params = [w1, b1, w2, b2, ...].  frame: as conv3x3."""
     if _native_bf16():
         from . import p8
-        if frame is not None:
-            frame.alive = False
+        _frame_end(frame)
         return p8.vgg_block_nchw(_chk(x.contiguous(), name="block input"), pool, params)
     if _OPERAND_ROUNDING == "bf16_emulate":    # layer by layer: every conv rounds its own operands
-        if frame is not None:
-            frame.alive = False
+        _frame_end(frame)
         for j in range(len(params) // 2):
             x = conv3x3(x, params[2 * j], params[2 * j + 1], True)
         return maxpool2x2(x) if pool else x

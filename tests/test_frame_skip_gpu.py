@@ -204,3 +204,139 @@ def test_run_step_is_bit_identical_with_and_without_skipping(monkeypatch):
         assert not diff, f"step {i}: metrics differ with / without skipping: {diff}"
     assert torch.equal(on[1], off[1]), "student.grad differs"
     assert torch.equal(on[2], off[2]), "student.flat differs"
+
+
+# ---------------------------------------------------------------------------- the branches of the forward launcher, one by one
+SCHED, LIST, FILL = "ptmi_conv3x3_wino4p_fwd_sched", "ptmi_conv3x3_wino4p_fwd_list", "ptmi_frame_fill"
+
+
+def _ring_next(rings, op, h, w):
+    nxt = torch.empty_like(rings)
+    _lib.call("ptmi_frame_ring_next", ctypes.c_void_p(rings.data_ptr()), ctypes.c_void_p(nxt.data_ptr()), int(rings.shape[0]), op, h, w)
+    return nxt
+
+
+def _case(cin, h, w, seed, n=3):
+    """(rings, input pattern on the device, framed input)"""
+    gen = torch.Generator().manual_seed(seed)
+    rings = _rings(h, w)
+    pat = torch.randn(cin, 4, 4, generator=gen).abs()
+    return gen, rings, pat.to(DEV), _framed(torch.randn(n, cin, h, w, generator=gen), rings, pat).to(DEV)
+
+
+def test_unsupported_kind_ends_the_frame(monkeypatch):
+    monkeypatch.setattr(ops, "_FRAME_CACHE", {})
+    h, w = 40, 152
+    assert ops._conv_kind(32, 32, (h, w)) == "wino"
+    gen, rings, pat, x = _case(32, h, w, 11)
+    wt, b = _layer(32, 32, gen)
+    with torch.no_grad():
+        want = ops.conv3x3(x, wt, b, True, None)
+        seen = _count_calls(monkeypatch)
+        frame = ops.FrameState(rings, pat, ("test", 0))
+        got = ops.conv3x3(x, wt, b, True, frame)
+    assert not torch.isnan(want).any() and torch.equal(got, want)
+    assert frame.alive is False
+    assert seen.count("ptmi_conv3x3_wino_fwd") == 1, seen               # the layer; no probe
+    assert LIST not in seen and FILL not in seen and SCHED not in seen and "ptmi_conv3x3_fwd" not in seen, seen
+
+
+def test_stem_then_a_wino4_layer(monkeypatch):
+    monkeypatch.setattr(ops, "_FRAME_CACHE", {})
+    monkeypatch.setattr(ops, "_FRAME_MIN_SHARE", 0.0)
+    h, w = 48, 333
+    assert ops._conv_kind(3, 64, (h, w)) == "mfma"
+    gen, rings, pat, x = _case(3, h, w, 12)
+    (w1, b1), (w2, b2) = _layer(3, 64, gen), _layer(64, 64, gen)
+    with torch.no_grad():
+        want = ops.conv3x3(ops.conv3x3(x, w1, b1, True, None), w2, b2, True, None)
+        seen = _count_calls(monkeypatch)
+        frame = ops.FrameState(rings, pat, ("test", 0))
+        y = ops.conv3x3(x, w1, b1, True, frame)
+        assert seen.count("ptmi_conv3x3_fwd") == 2, seen                 # the probe canvas, then the layer
+        assert LIST not in seen and FILL not in seen, seen
+        assert frame.alive is True
+        assert torch.equal(frame.rings, _ring_next(rings, 0, h, w))
+        assert frame.pattern.shape == (64, 4, 4)
+        del seen[:]
+        got = ops.conv3x3(y, w2, b2, True, frame)
+    assert seen.count(LIST) == 1 and seen.count(FILL) == 1, seen
+    assert not torch.isnan(want).any() and torch.equal(got, want)
+
+
+def test_share_below_the_bar_takes_the_plain_launch(monkeypatch):
+    monkeypatch.setattr(ops, "_FRAME_CACHE", {})
+    monkeypatch.setattr(ops, "_FRAME_MIN_SHARE", 0.99)
+    h, w = 48, 333
+    gen, rings, pat, x = _case(64, h, w, 13)
+    wt, b = _layer(64, 64, gen)
+    with torch.no_grad():
+        want = ops.conv3x3(x, wt, b, True, None)
+        seen = _count_calls(monkeypatch)
+        frame = ops.FrameState(rings, pat, ("test", 0))
+        got = ops.conv3x3(x, wt, b, True, frame)
+    assert not torch.isnan(want).any() and torch.equal(got, want)
+    assert seen.count(SCHED) == 2, seen                                  # one probe, one plain launch of the layer
+    assert LIST not in seen and FILL not in seen, seen
+    assert frame.alive is False
+
+
+@pytest.mark.parametrize("with_frame", [True, False], ids=["frame", "no_frame"])
+def test_pack_mismatch_raises_before_any_launch(monkeypatch, with_frame):
+    monkeypatch.setattr(ops, "_FRAME_CACHE", {})
+    h, w = 48, 333
+    gen, rings, pat, x = _case(64, h, w, 14)
+    wt, b = _layer(64, 64, gen)
+    wp = ops.conv3x3_pack(wt, 0, 1, (h, w))
+    wrong = torch.zeros(wp.numel() + 1, device=DEV)
+    frame = ops.FrameState(rings, pat, ("test", 0)) if with_frame else None
+    seen = _count_calls(monkeypatch)
+    with pytest.raises(_lib.PtmiError, match="packed weights"):
+        ops.conv3x3_raw(x, wrong, b, None, 64, 1, frame, None)
+    assert seen == []
+
+
+def test_probe_cache(monkeypatch):
+    """a frozen layer behind a keyed pattern probes once; a new parameter version, or a pattern without a key, probes again.  The
+    first call is the probe (one plain launch, of the canvas) and the list + fill of the layer -- no second plain launch."""
+    monkeypatch.setattr(ops, "_FRAME_CACHE", {})
+    monkeypatch.setattr(ops, "_FRAME_MIN_SHARE", 0.0)
+    h, w = 40, 152
+    gen, rings, pat, x = _case(64, h, w, 15)
+    wt, b = _layer(64, 64, gen)
+    assert not wt.requires_grad and not b.requires_grad
+    want = ops.conv3x3(x, wt, b, True, None)
+    assert not torch.isnan(want).any()
+    seen = _count_calls(monkeypatch)
+
+    def call(key, probes):
+        del seen[:]
+        frame = ops.FrameState(rings, pat, key)
+        got = ops.conv3x3(x, wt, b, True, frame)
+        assert (seen.count(SCHED), seen.count(LIST), seen.count(FILL)) == (probes, 1, 1), seen
+        assert torch.equal(got, want)
+        return frame
+
+    assert call(("test", 0), 1).key is not None
+    assert len(ops._FRAME_CACHE) == 1
+    call(("test", 0), 0)
+    wt.mul_(1.0)                                   # same values, next version
+    call(("test", 0), 1)
+    call(("test", 0), 0)
+    assert call(None, 1).key is None
+    call(None, 1)
+    assert len(ops._FRAME_CACHE) == 2
+
+
+def test_fused_pool_advances_through_conv_and_pool(monkeypatch):
+    monkeypatch.setattr(ops, "_FRAME_CACHE", {})
+    h, w = 48, 333
+    gen, rings, pat, x = _case(64, h, w, 16)
+    wt, b = _layer(64, 64, gen)
+    want = ops.conv3x3_relu_pool_nograd(x, wt, b, None)
+    frame = ops.FrameState(rings, pat, ("test", 0))
+    got = ops.conv3x3_relu_pool_nograd(x, wt, b, frame)
+    assert not torch.isnan(want).any() and torch.equal(got, want)
+    assert torch.equal(frame.rings, _ring_next(_ring_next(rings, 2, h, w), 1, h, w))
+    assert frame.pattern.shape == (64, 4, 4)
+    assert frame.key is not None
