@@ -6,7 +6,10 @@ two-crop mapper, aspect-ratio grouping of the labelled and the unlabelled stream
 
 cfg.DATALOADER.NUM_WORKERS (the reference's DataLoader worker processes, build.py:205-216) is the number of decode THREADS of
 data/prefetch.py: 0 decodes and maps image by image on the consuming thread; n > 0 decodes ahead and maps a chunk of images
-per call.  The record stream is the same for every value."""
+per call.  The record stream is the same for every value.
+
+image_cache (data/cache.py, off by default): both loaders read a file that is resident on the device from there instead of
+decoding it, and insert what they decode; the records are the same with and without it."""
 import collections
 import itertools
 from typing import Iterable, Iterator, List, Optional
@@ -39,9 +42,21 @@ def training_sampler(size: int, seed: int = 0, shuffle: bool = True) -> Iterator
     return itertools.islice(stream(), rank, None, world)
 
 
-def _mapped_pairs(dicts: List[dict], sampler: Iterable[int], mapper: DeviceTwoCropMapper, fmt: str, labelled: bool):
+def _cached_image(cache, file_name: str, fmt: str) -> torch.Tensor:
+    """`datasets.read_image` on the cache's device through the cache (the serial path): a miss is decoded here and its
+    host -> device copy -- the one the mapper would make -- is what the cache keeps"""
+    key, img = cache.lookup(file_name, fmt == "BGR")
+    if img is None:
+        img = datasets.read_image(file_name, fmt).to(cache.device)
+        cache.insert(key, img)
+    return img
+
+
+def _mapped_pairs(dicts: List[dict], sampler: Iterable[int], mapper: DeviceTwoCropMapper, fmt: str, labelled: bool,
+                  image_cache=None):
     for i in sampler:
-        d = datasets.to_mapper_input(dicts[i], fmt)
+        img = None if image_cache is None else _cached_image(image_cache, dicts[i]["file_name"], fmt)
+        d = datasets.to_mapper_input(dicts[i], fmt, image=img)
         if not labelled:                     # the unlabelled stream's annotations are never used (trainer.py:248-257)
             d = _drop_annotations(d)
         yield mapper([d])[0]
@@ -91,10 +106,26 @@ def _closing(it, ahead):
         ahead.close()
 
 
-def build_detection_semisup_train_loader_two_crops(cfg, mapper: Optional[DeviceTwoCropMapper] = None, seed: Optional[int] = None):
+def _decode_ahead(items, workers: int, in_flight: int, device, fmt: str, image_cache):
+    if image_cache is None:
+        return prefetch.DecodeAhead(items, lambda d: d["file_name"], workers, in_flight, device)
+    return prefetch.DecodeAhead(items, lambda d: d["file_name"], workers, in_flight, device, cache=image_cache, bgr=fmt == "BGR")
+
+
+def _check_cache_device(cfg, image_cache) -> None:
+    if image_cache is None:
+        return
+    dev = torch.device(cfg.MODEL.DEVICE)
+    if dev.type != image_cache.device.type or dev.index not in (None, image_cache.device.index):
+        raise ValueError(f"image_cache is on {image_cache.device}, the loader works on MODEL.DEVICE {cfg.MODEL.DEVICE}")
+
+
+def build_detection_semisup_train_loader_two_crops(cfg, mapper: Optional[DeviceTwoCropMapper] = None, seed: Optional[int] = None,
+                                                   image_cache=None):
     """build.py:107-217: yields (label_strong, label_weak, unlabel_strong, unlabel_weak) lists of records forever.
     seed None: cfg.SEED when it is >= 0, else 0.  The index streams use the value itself on every rank (they are sharded by
-    rank), the mapper adds its per-rank offset."""
+    rank), the mapper adds its per-rank offset.  image_cache: a DeviceImageCache on MODEL.DEVICE, or None."""
+    _check_cache_device(cfg, image_cache)
     rank, world = _rank_world()
     seed = loader_seed(cfg, seed)
     bl, bu = cfg.SOLVER.IMG_PER_BATCH_LABEL, cfg.SOLVER.IMG_PER_BATCH_UNLABEL
@@ -108,21 +139,24 @@ def build_detection_semisup_train_loader_two_crops(cfg, mapper: Optional[DeviceT
     samp_l, samp_u = training_sampler(len(label_dicts), seed), training_sampler(len(unlabel_dicts), seed + 1)
     bl, bu = bl // world, bu // world
     if workers == 0:
-        lab = _mapped_pairs(label_dicts, samp_l, mapper, fmt, True)
-        unl = _mapped_pairs(unlabel_dicts, samp_u, mapper, fmt, False)
+        lab = _mapped_pairs(label_dicts, samp_l, mapper, fmt, True, image_cache)
+        unl = _mapped_pairs(unlabel_dicts, samp_u, mapper, fmt, False, image_cache)
         return iter(AspectRatioGroupedSemiSupDatasetTwoCrop((lab, unl), (bl, bu)))
     lab, unl, ahead = _prefetched_pairs(
         label_dicts, unlabel_dicts, samp_l, samp_u, mapper, fmt, min(bl, bu),
-        lambda items: prefetch.DecodeAhead(items, lambda d: d["file_name"], workers, prefetch.max_in_flight(bl + bu), cfg.MODEL.DEVICE))
+        lambda items: _decode_ahead(items, workers, prefetch.max_in_flight(bl + bu), cfg.MODEL.DEVICE, fmt, image_cache))
     return _closing(AspectRatioGroupedSemiSupDatasetTwoCrop((lab, unl), (bl, bu)), ahead)
 
 
-def _test_record(cfg, d: dict, m: dict, dev) -> dict:
+def _test_record(cfg, d: dict, m: dict, dev, shared: bool = False) -> dict:
+    """shared: m["image"] may live in an image cache, so the record must not be that tensor itself"""
     img = m["image"].to(dev)
     h, w = img.shape[-2:]
     nh, nw = resize_shortest_edge_size(h, w, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
-    rec = {"image": resize_batch([img], [(nh, nw)])[0], "height": h, "width": w, "image_id": d["image_id"],
-           "file_name": d["file_name"]}
+    out = resize_batch([img], [(nh, nw)])[0]
+    if shared and out is img:                         # already at its test size: the resize hands its source back
+        out = out.clone()
+    rec = {"image": out, "height": h, "width": w, "image_id": d["image_id"], "file_name": d["file_name"]}
     if "boxes" in m:
         inst = FreeInstances((h, w))
         inst.gt_boxes, inst.gt_classes, inst.difficult = Boxes(m["boxes"]), m["classes"], m["difficult"]
@@ -133,32 +167,38 @@ def _test_record(cfg, d: dict, m: dict, dev) -> dict:
     return rec
 
 
-def build_detection_test_loader(cfg, dataset_name: str, batch_size: int = 1):
+def build_detection_test_loader(cfg, dataset_name: str, batch_size: int = 1, image_cache=None):
     """D2 build_detection_test_loader + DatasetMapper(is_train=False): ResizeShortestEdge(MIN_SIZE_TEST, MAX_SIZE_TEST), no flip;
     records keep the ORIGINAL height / width (detector_postprocess scales the detections back) and carry the ground truth in
     original coordinates for the evaluator.  Rank r evaluates images r, r + world, ... (D2 InferenceSampler shards contiguously;
     the evaluator gathers the shards, so the split does not matter).  With DATALOADER.NUM_WORKERS > 0 the images are decoded
-    ahead by that many threads (look-ahead: LOOKAHEAD_STEPS x max(batch_size, workers) images); the records are the same."""
+    ahead by that many threads (look-ahead: LOOKAHEAD_STEPS x max(batch_size, workers) images); the records are the same.
+    image_cache: a DeviceImageCache on MODEL.DEVICE, or None; the one the train loader uses may be passed."""
     rank, world = _rank_world()
+    _check_cache_device(cfg, image_cache)
     workers = prefetch.num_workers(cfg)
     dicts = datasets.get_dataset_dicts([dataset_name])
     dev = torch.device(cfg.MODEL.DEVICE)
     mine = dicts[rank::world]
     fmt = cfg.INPUT.FORMAT
 
+    shared = image_cache is not None
+
     def serial():
         for s in range(0, len(mine), batch_size):
-            yield [_test_record(cfg, d, datasets.to_mapper_input(d, fmt, is_train=False), dev) for d in mine[s:s + batch_size]]
+            yield [_test_record(cfg, d, datasets.to_mapper_input(
+                d, fmt, image=_cached_image(image_cache, d["file_name"], fmt) if shared else None, is_train=False), dev, shared)
+                for d in mine[s:s + batch_size]]
 
     def ahead_of_time():
-        ahead = prefetch.DecodeAhead(mine, lambda d: d["file_name"], workers,
-                                     prefetch.max_in_flight(max(batch_size, workers)), dev)
+        ahead = _decode_ahead(mine, workers, prefetch.max_in_flight(max(batch_size, workers)), dev, fmt, image_cache)
         try:
             while True:
                 got = ahead.take_planar(batch_size, fmt == "BGR")
                 if not got:
                     return
-                yield [_test_record(cfg, d, datasets.to_mapper_input(d, fmt, image=img, is_train=False), dev) for d, img in got]
+                yield [_test_record(cfg, d, datasets.to_mapper_input(d, fmt, image=img, is_train=False), dev, shared)
+                       for d, img in got]
         finally:
             ahead.close()
     return serial() if workers == 0 else ahead_of_time()

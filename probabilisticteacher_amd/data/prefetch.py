@@ -8,7 +8,12 @@ here that work is on the device).  All randomness and every device call stay on 
 does not depend on the number of workers.
 
 Bounds: at most LOOKAHEAD_STEPS steps' worth of images (`max_in_flight`) are submitted and not yet handed back, and the ring
-holds at most that many pinned slabs, each as large as the largest image it has carried."""
+holds at most that many pinned slabs, each as large as the largest image it has carried.
+
+With a `DeviceImageCache` (data/cache.py) a file that is already resident is not decoded at all: its ticket is done when it is
+submitted, takes no slab and no worker, and planar() hands out the cached tensor.  The misses are decoded, copied and unpacked
+as without a cache, and the tensors that one unpack launch wrote are what the cache keeps.  Only the consuming thread looks
+into the cache or inserts."""
 import collections
 import queue
 import threading
@@ -46,11 +51,13 @@ class _Slab:
 
 
 class _Ticket:
-    __slots__ = ("item", "file_name", "slab", "array", "error", "done")
+    __slots__ = ("item", "file_name", "slab", "array", "error", "done", "key", "image")
 
     def __init__(self, item, file_name: str, slab: Optional[_Slab]):
         self.item, self.file_name, self.slab = item, file_name, slab
         self.array: Optional[np.ndarray] = None      # (H, W, 3) uint8: a view of the slab, or the decoder's own array
+        self.key = None                              # with an image cache: the file's key there
+        self.image: Optional[torch.Tensor] = None    # a cache hit: the resident (3, H, W) tensor, and nothing to decode
         self.error: Optional[BaseException] = None
         self.done = threading.Event()
 
@@ -91,10 +98,16 @@ class DecodeAhead:
 
     take(n) hands out the next up to n items with their decoded images, in the order of `items`; planar() turns what was taken
     into (3, H, W) tensors on `device`; release() gives the slabs back.  Everything but the decode itself runs on the calling
-    thread.  The worker threads are daemons and hold no reference to this object: close(), or dropping the object, stops them."""
+    thread.  The worker threads are daemons and hold no reference to this object: close(), or dropping the object, stops them.
 
-    def __init__(self, items: Iterable, file_of: Callable[[object], str], workers: int, in_flight: int, device):
+    cache: a DeviceImageCache on `device`; `bgr` is then the channel order planar() will be asked for (it is part of the key,
+    and a hit is decided at submission)."""
+
+    def __init__(self, items: Iterable, file_of: Callable[[object], str], workers: int, in_flight: int, device,
+                 cache=None, bgr: Optional[bool] = None):
         assert workers > 0 and in_flight > 0
+        assert cache is None or bgr is not None, "with a cache the channel order is fixed when the object is made"
+        self._cache, self._bgr = cache, bgr
         self._items = iter(items)
         self._file_of = file_of
         self._bound = in_flight
@@ -135,9 +148,15 @@ class DecodeAhead:
             except StopIteration:
                 self._exhausted = True
                 return
-            ticket = _Ticket(item, self._file_of(item), self._slab())
+            file_name = self._file_of(item)
+            key, image = self._cache.lookup(file_name, self._bgr) if self._cache is not None else (None, None)
+            ticket = _Ticket(item, file_name, self._slab() if image is None else None)
+            ticket.key, ticket.image = key, image
             self._pending.append(ticket)
-            self._tasks.put(ticket)
+            if image is None:
+                self._tasks.put(ticket)
+            else:                                   # resident: done as submitted, no slab, no task; it keeps its place in line
+                ticket.done.set()
 
     def take(self, n: int, multiple: int = 1) -> List[_Ticket]:
         """The next up to n tickets (fewer at the end of `items`), a multiple of `multiple` of them.  A failed decode raises
@@ -166,7 +185,18 @@ class DecodeAhead:
 
     def planar(self, tickets: List[_Ticket], bgr: bool) -> List[torch.Tensor]:
         """what `datasets.read_image` returns for the taken images, on the device: one async copy per image and one unpack
-        launch for all of them ("cpu": the reorder of read_image itself)"""
+        launch for all of them ("cpu": the reorder of read_image itself).  With a cache only the misses are copied and
+        unpacked, the cache keeps what the launch wrote, and hits and misses come back in ticket order."""
+        if self._cache is None:
+            return self._unpack(tickets, bgr)
+        assert bool(bgr) == bool(self._bgr), "the cache was keyed for the other channel order"
+        misses = [t for t in tickets if t.image is None]
+        for t, img in zip(misses, self._unpack(misses, bgr) if misses else ()):
+            t.image = img
+            self._cache.insert(t.key, img)
+        return [t.image for t in tickets]
+
+    def _unpack(self, tickets: List[_Ticket], bgr: bool) -> List[torch.Tensor]:
         if not self._pinned:
             return [torch.from_numpy(np.ascontiguousarray((t.array[:, :, ::-1] if bgr else t.array).transpose(2, 0, 1)))
                     for t in tickets]
@@ -187,7 +217,7 @@ class DecodeAhead:
         for t in tickets:
             if t.slab is not None:
                 self._free.append(t.slab)
-            t.array = t.slab = None
+            t.array = t.slab = t.image = None
         self._held -= len(tickets)
         self._top_up()
 

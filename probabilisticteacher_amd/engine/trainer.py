@@ -23,6 +23,11 @@ from .flat import BucketedGradReducer, FlatParams, broadcast_, segment_offsets
 
 
 class PTrainer:
+    # The process's DeviceImageCache (data/cache.py) or None: `build_train_loader` and `build_test_loader` are classmethods, as
+    # in D2, so the one cache they share -- the train loader, and the student and the teacher evaluation of every EvalHook -- is
+    # set on the class (train_net.py --image-cache-gb).  None: every file is decoded whenever it is read.
+    image_cache = None
+
     @staticmethod
     def ddp_wgrad_waves(amp: bool) -> int:
         """weight-gradient waves PTrainer selects while a gradient exchange is active"""
@@ -398,12 +403,12 @@ class PTrainer:
         """trainer.py:139-141 -> pt/data/build.py:107: the two-crop semi-supervised loader over cfg.DATASETS.TRAIN_LABEL /
         TRAIN_UNLABEL (device-side mapper, data/build.py)"""
         from ..data import build_detection_semisup_train_loader_two_crops
-        return build_detection_semisup_train_loader_two_crops(cfg)
+        return build_detection_semisup_train_loader_two_crops(cfg, image_cache=cls.image_cache)
 
     @classmethod
     def build_test_loader(cls, cfg, dataset_name):
         from ..data import build_detection_test_loader
-        return build_detection_test_loader(cfg, dataset_name)
+        return build_detection_test_loader(cfg, dataset_name, image_cache=cls.image_cache)
 
     @classmethod
     def test(cls, cfg, model, data_loader=None, class_names=None, is_2007: bool = False):

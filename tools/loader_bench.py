@@ -1,12 +1,15 @@
 """How many source images per second does the two-crop train loader deliver from files, with no model behind it?
 
     python tools/loader_bench.py [--root DIR] [--workers 0,2,4,8,16] [--records 200] [--min-seconds 2] [--warmup-batches 2] [--out FILE]
+                                 [--image-cache-gb G]
 
 Writes (once; an existing --root is reused) VOC-layout datasets of generated images with Pillow and a fixed seed -- PNG and
 JPEG, at 2048x1024 (Cityscapes) and 1242x375 (KITTI) -- and times `build_detection_semisup_train_loader_two_crops` of
 configs/pt/final_c2f.yaml (16 + 16 images per batch, MIN_SIZE_TRAIN 600) on each of them for every DATALOADER.NUM_WORKERS
 asked for: records/s = source images (labelled + unlabelled) consumed per second over >= --records records and >= --min-seconds
-after the warm-up batches, the device drained at both ends.  One JSON line per leg; the step needs 32 records per step time."""
+after the warm-up batches, the device drained at both ends.  One JSON line per leg; the step needs 32 records per step time.
+--image-cache-gb G adds, after every leg, the same leg through a DeviceImageCache (data/cache.py): a first pass fills the cache,
+the second pass is the one timed, and the line says how many of its reads were hits."""
 import argparse
 import json
 import os
@@ -62,16 +65,30 @@ def write_dataset(root, fmt, h, w, seed):
         f.write("\n".join(ids) + "\n")
 
 
-def time_loader(case, workers, records, min_seconds, warmup_batches, device):
+def time_loader(case, workers, records, min_seconds, warmup_batches, device, cache_gb=0.0):
+    """cache_gb > 0: the cached leg -- a first pass (not timed) runs until every file of both datasets is resident in a
+    DeviceImageCache of that budget, or until 4 epochs' worth of records have gone by if the budget holds fewer; the timed
+    pass that follows is the steady state"""
     cfg = setup_cfg("configs/pt/final_c2f.yaml", [
         "MODEL.DEVICE", device, "DATASETS.TRAIN_LABEL", (f"lb_{case}_label",), "DATASETS.TRAIN_UNLABEL", (f"lb_{case}_unlabel",),
         "DATALOADER.NUM_WORKERS", workers])
     per_batch = cfg.SOLVER.IMG_PER_BATCH_LABEL + cfg.SOLVER.IMG_PER_BATCH_UNLABEL
     need = -(-records // per_batch)
-    loader = build_detection_semisup_train_loader_two_crops(cfg, seed=3)
+    cache = None
+    if cache_gb > 0:
+        from probabilisticteacher_amd.data import DeviceImageCache
+        cache = DeviceImageCache(int(cache_gb * 1e9), device)
+        loader = build_detection_semisup_train_loader_two_crops(cfg, seed=3, image_cache=cache)
+        fill = 0
+        while len(cache) < 2 * N_FILES and fill * per_batch < 4 * 2 * N_FILES:
+            next(loader)
+            fill += 1
+    else:
+        loader = build_detection_semisup_train_loader_two_crops(cfg, seed=3)
     for _ in range(warmup_batches):
         next(loader)
     torch.cuda.synchronize()
+    hits0, misses0 = (cache.hits, cache.misses) if cache is not None else (0, 0)
     t0, c0 = time.perf_counter(), time.thread_time()
     batches = 0
     while batches < need or time.perf_counter() - t0 < min_seconds:
@@ -80,11 +97,16 @@ def time_loader(case, workers, records, min_seconds, warmup_batches, device):
     c1 = time.thread_time()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    timed = (cache.hits - hits0, cache.misses - misses0) if cache is not None else None
     if hasattr(loader, "close"):
         loader.close()
-    return {"case": case, "workers": workers, "records": batches * per_batch, "seconds": round(dt, 4),
-            "records_per_s": round(batches * per_batch / dt, 2), "ms_per_batch": round(1e3 * dt / batches, 2),
-            "consumer_thread_cpu_ms_per_batch": round(1e3 * (c1 - c0) / batches, 2)}
+    out = {"case": case, "workers": workers, "records": batches * per_batch, "seconds": round(dt, 4),
+           "records_per_s": round(batches * per_batch / dt, 2), "ms_per_batch": round(1e3 * dt / batches, 2),
+           "consumer_thread_cpu_ms_per_batch": round(1e3 * (c1 - c0) / batches, 2)}
+    if cache is not None:
+        out.update(image_cache_gb=cache_gb, cached_images=len(cache), cache_bytes_used=cache.bytes_used,
+                   timed_pass_hits=timed[0], timed_pass_misses=timed[1])
+    return out
 
 
 def main():
@@ -97,6 +119,9 @@ def main():
     ap.add_argument("--cases", default=",".join(c[0] for c in CASES))
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
+    ap.add_argument("--image-cache-gb", type=float, default=0.0,
+                    help="> 0: after each leg, the same leg with a DeviceImageCache of this budget -- the first pass fills it, "
+                         "the second is timed (48 files of 2048x1024 are 0.30 GB)")
     ap.add_argument("--write-only", action="store_true", help="write the missing datasets under --root and stop")
     args = ap.parse_args()
     tmp = None
@@ -121,11 +146,13 @@ def main():
             datasets.register_pascal_voc(f"lb_{case}_{part}", os.path.join(root, case, part), "train", ("car",))
     for case in wanted:
         for workers in (int(v) for v in args.workers.split(",")):
-            line = json.dumps(time_loader(case, workers, args.records, args.min_seconds, args.warmup_batches, args.device))
-            print(line, flush=True)
-            if args.out:
-                with open(args.out, "a") as f:
-                    f.write(line + "\n")
+            for cache_gb in (0.0, args.image_cache_gb) if args.image_cache_gb > 0 else (0.0,):
+                line = json.dumps(time_loader(case, workers, args.records, args.min_seconds, args.warmup_batches, args.device,
+                                              cache_gb))
+                print(line, flush=True)
+                if args.out:
+                    with open(args.out, "a") as f:
+                        f.write(line + "\n")
     if tmp is not None:
         tmp.cleanup()
 

@@ -53,6 +53,9 @@ def main():
                     help="register a VOC-format directory as dataset NAME (Annotations/, JPEGImages/, ImageSets/Main/SPLIT.txt)")
     ap.add_argument("--register-coco", action="append", default=[], metavar="NAME=JSON:IMAGE_ROOT",
                     help="register a COCO-format json (images under IMAGE_ROOT) as dataset NAME")
+    ap.add_argument("--image-cache-gb", type=float, default=0.0, metavar="G",
+                    help="keep up to G GB of decoded images on this rank's device, so that every file is decoded once (the train "
+                         "loader and all evaluations share the cache; nothing is evicted; 0 = off)")
     ap.add_argument("opts", nargs=argparse.REMAINDER)
     args = ap.parse_args()
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("LOCAL_RANK", 0), ("WORLD_SIZE", 1)))
@@ -77,6 +80,11 @@ def main():
     seed_all_rng(None if cfg.SEED < 0 else cfg.SEED + rank)    # D2 default_setup
     if cfg.SEED < 0:
         torch.manual_seed(0)                                   # (without a SEED the initial weights stay those of seed 0)
+    if args.image_cache_gb < 0:
+        raise ValueError(f"--image-cache-gb must not be negative, got {args.image_cache_gb}")
+    if args.image_cache_gb > 0 and not args.synthetic:
+        from probabilisticteacher_amd.data import DeviceImageCache
+        PTrainer.image_cache = DeviceImageCache(int(args.image_cache_gb * 1e9), cfg.MODEL.DEVICE)    # one per process = per rank
     if args.synthetic:
         loader = synthetic_loader(cfg, torch.device("cuda", local), rank, world)
     else:
@@ -118,6 +126,8 @@ def main():
             checkpoint.save_checkpoint(trainer, os.path.join(cfg.OUTPUT_DIR, "model_before_anomaly.pth"),
                                        iteration=trainer.iter - 1, tag_last=False)
         sys.exit(f"AnomalyError: {e}")
+    if PTrainer.image_cache is not None and rank == 0:
+        print(PTrainer.image_cache, flush=True)               # images, bytes, hits and misses of rank 0's cache
     if world > 1:
         dist.destroy_process_group()
 
