@@ -530,6 +530,32 @@ int ptmi_roi_infer_class_collect(const float* sorted_keys, const int32_t* order,
                                  int max_keep, int64_t total, float* dense_keys_out, int32_t* img_kept_out,
                                  ptmi_stream_t s);
 
+/* ------------------------------------------------------------------ test-time augmentation (TEST.AUG)
+ * detectron2 0.5 GeneralizedRCNNWithTTA._inverse_boxes + _merge_detections up to the NMS call, for the D detections of ALL
+ * augmentations of a batch of nimg images: boxes (D,4) / scores (D) in augmented-image coordinates, concatenated in
+ * augmentation order, augmentations grouped by image (an image's detections are one contiguous segment).  aug_offsets
+ * (naug+1) int32: detections [aug_offsets[a], aug_offsets[a+1]) belong to augmentation a.  aug_meta (naug,3) int32 = image,
+ * flipped, has pre-transform; aug_factors (naug,5) float = w_s, fx_s = fp32(w / w_s), fy_s = fp32(h / h_s), gx = fp32(W / w),
+ * gy = fp32(H / h) (formed in double on the host, rounded once).  Per detection, every step its own fp32 operation, never
+ * contracted: flipped: x = w_s - x; x *= fx_s, y *= fy_s; has pre-transform: x *= gx, y *= gy; min / max per axis after each
+ * step (apply_box).  Then fast_rcnn_inference_single_image: a row with a non-finite coordinate or score is dropped, boxes are
+ * clipped to image_sizes_hw[image] = (H, W), rows with score > score_thresh (strict) are the candidates.
+ * Outputs: boxes_out (D,4) mapped and clipped ((0,0,0,0) for a row the finite filter dropped); keys_out (D) = score of a
+ * candidate, -inf otherwise (a stable descending sort per image lists the candidates first, in batched_nms order);
+ * img_count_out (nimg) = candidates, img_max_out (nimg) = their largest coordinate -- an integer max on the bits of the
+ * non-negative floats: the same bits on every run.  All table entries device arrays; d == 0 only clears the two per-image
+ * outputs. */
+int ptmi_tta_map_boxes(const float* boxes, const float* scores, const int32_t* aug_offsets, const int32_t* aug_meta,
+                       const float* aug_factors, const float* image_sizes_hw, float* boxes_out, float* keys_out,
+                       float* img_max_out, int32_t* img_count_out, int64_t d, int naug, int nimg, float score_thresh,
+                       ptmi_stream_t s);
+/* torchvision batched_nms class offset for the merged detections: out[beg_i + p] = boxes[beg_i + order[beg_i + p]] +
+ * classes[beg_i + order[beg_i + p]] * (img_max[i] + 1) in fp32 (the rounding of ptmi_roi_infer_nms_boxes), for the per-image
+ * segments seg_offsets (nimg+1); classes (D) int64; order = index within the segment from the segmented sort of keys_out;
+ * max_count = largest segment. */
+int ptmi_tta_nms_boxes(const float* boxes, const int64_t* classes, const int32_t* order, const int32_t* seg_offsets,
+                       const float* img_max, int nimg, int max_count, float* out, ptmi_stream_t s);
+
 /* ------------------------------------------------------------------ COCO evaluation: detection <-> ground-truth matching
  * pycocotools COCOeval.computeIoU / evaluateImg with maskApi.c bbIou (detectron2 COCOEvaluator, pt/engine/trainer.py:132-133)
  * for ALL nseg (image, category) segments of an evaluation in one launch.  Segment i holds detections

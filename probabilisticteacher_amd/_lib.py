@@ -126,6 +126,8 @@ SIGNATURES = {
     "ptmi_roi_infer_class_keys": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ptmi_roi_infer_class_nms_boxes": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "ptmi_roi_infer_class_collect": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp]),
+    "ptmi_tta_map_boxes": (_i, [_vp] * 10 + [_i64, _i, _i, _f, _vp]),
+    "ptmi_tta_nms_boxes": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "ptmi_coco_match_max_gt": (_i, []),
     "ptmi_coco_match": (_i, [_vp] * 7 + [_i64, _i64, _i64, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ptmi_bce_logits_sum": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _vp, _vp]),

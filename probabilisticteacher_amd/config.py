@@ -165,7 +165,10 @@ def get_cfg() -> CfgNode:
                            CROP=CfgNode(dict(ENABLED=False, TYPE="relative_range", SIZE=[0.9, 0.9]))))       # D2 0.5 defaults
     C.DATASETS = CfgNode(dict(TRAIN=(), TEST=()))
     C.DATALOADER = CfgNode(dict(NUM_WORKERS=4, FILTER_EMPTY_ANNOTATIONS=True))      # D2 default: True
-    C.TEST = CfgNode(dict(DETECTIONS_PER_IMAGE=100, EVAL_PERIOD=0))
+    # TEST.AUG: D2 0.5 test-time augmentation (modeling/tta.py validates the values where the wrapper is built)
+    C.TEST = CfgNode(dict(DETECTIONS_PER_IMAGE=100, EVAL_PERIOD=0,
+                          AUG=dict(ENABLED=False, MIN_SIZES=(400, 500, 600, 700, 800, 900, 1000, 1100, 1200), MAX_SIZE=4000,
+                                   FLIP=True)))
     C.SOLVER = CfgNode(dict(
         LR_SCHEDULER_NAME="WarmupMultiStepLR", MAX_ITER=40000, BASE_LR=0.001, MOMENTUM=0.9, NESTEROV=False,
         WEIGHT_DECAY=0.0001, WEIGHT_DECAY_NORM=0.0, GAMMA=0.1, STEPS=(30000,), WARMUP_FACTOR=1.0 / 1000,

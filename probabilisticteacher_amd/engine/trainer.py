@@ -435,6 +435,19 @@ class PTrainer:
             results = list(results.values())[0]
         return results
 
+    @classmethod
+    def test_with_TTA(cls, cfg, model, data_loader=None, class_names=None, is_2007: bool = False):
+        """D2 tools/train_net.py Trainer.test_with_TTA: `test` over the model wrapped in GeneralizedRCNNWithTTA (TEST.AUG:
+        multi-scale + flip, modeling/tta.py), under the same operand rounding; every top-level key of the results gets the
+        suffix `_TTA` ("bbox_TTA").  The model's train / eval mode is restored."""
+        from ..modeling.tta import GeneralizedRCNNWithTTA
+        was_training = model.training
+        try:
+            res = cls.test(cfg, GeneralizedRCNNWithTTA(cfg, model), data_loader, class_names, is_2007)
+        finally:
+            model.train(was_training)
+        return None if res is None else {k + "_TTA": v for k, v in res.items()}
+
     # ------------------------------------------------------------------ trainer shell (trainer.py:466-547)
     def resume_or_load(self, resume: bool = False):
         """trainer.py:466-496: weights (resume=False) or weights + optimiser + iteration (resume=True) from

@@ -68,14 +68,18 @@ class GuassianGeneralizedRCNN(nn.Module):
             pat = self._frame_colours[colour] = ops.preprocess_images([probe], self._mean, self._std)[0, :, :4, :4].contiguous()
         return ops.FrameState(rings, pat, ("image", colour, tuple(self._mean), tuple(self._std)))
 
-    def inference(self, batched_inputs):
+    def inference(self, batched_inputs, do_postprocess: bool = True):
         """Eval-mode path (rcnn.py:33-34 -> D2 GeneralizedRCNN.inference + detector_postprocess):
-        test-time RPN (6000 -> 1000 proposals), ROI inference, boxes rescaled to each record's height/width."""
+        test-time RPN (6000 -> 1000 proposals), ROI inference, boxes rescaled to each record's height/width.
+        do_postprocess=False (D2's keyword, used by modeling/tta.py): the list of Instances as the ROI heads return them, in
+        the coordinates of the network input."""
         assert not self.training
         images = self.preprocess_image(batched_inputs)
         features = self.backbone(images.tensor)
         proposals, _ = self.proposal_generator(images, features, None)
         results, _ = self.roi_heads(images, features, proposals, None)
+        if not do_postprocess:
+            return results
         out = []
         for res, rec, size in zip(results, batched_inputs, images.image_sizes):
             out.append({"instances": detector_postprocess(res, rec.get("height", size[0]), rec.get("width", size[1]))})

@@ -1607,6 +1607,114 @@ def roi_infer_nms_boxes(boxes, order, seg_offsets, img_max, max_count: int, k: i
     return out
 
 
+# ---- test-time augmentation (TEST.AUG): map every augmentation's detections back, one merged NMS per image
+TTA_SCORE_THRESH = 1e-8          # D2 0.5 GeneralizedRCNNWithTTA._merge_detections
+
+
+def _tta_tables(aug_rows, aug_counts, image_sizes, d: int):
+    """Host side of the per-augmentation table: aug_rows[a] = (image, flipped, w_s, fx_s, fy_s, gx, gy, has pre-transform),
+    aug_counts[a] = its detections.  Checks everything a kernel indexes with and returns (offsets, meta, factors, per-image
+    segment lengths) as host lists."""
+    nimg = len(image_sizes)
+    if len(aug_rows) != len(aug_counts) or not aug_rows or nimg == 0:
+        raise ValueError(f"tta: {len(aug_rows)} augmentation rows, {len(aug_counts)} counts, {nimg} images")
+    offs, meta, fact, lengths, prev = [0], [], [], [0] * nimg, 0
+    for row, c in zip(aug_rows, aug_counts):
+        img, flip, w_s, fx, fy, gx, gy, pre = row
+        img, c = int(img), int(c)
+        if not (prev <= img < nimg) or c < 0:
+            raise ValueError(f"tta: augmentation rows must be grouped by image in ascending order (image {img} after {prev}, "
+                             f"{nimg} images) with non-negative counts (got {c})")
+        prev = img
+        offs.append(offs[-1] + c)
+        lengths[img] += c
+        meta.append([img, int(bool(flip)), int(bool(pre))])
+        fact.append([float(w_s), float(fx), float(fy), float(gx), float(gy)])
+    if offs[-1] != d:
+        raise ValueError(f"tta: the augmentations hold {offs[-1]} detections, the arrays {d}")
+    return offs, meta, fact, lengths
+
+
+def tta_map_boxes(boxes: torch.Tensor, scores: torch.Tensor, aug_rows, aug_counts: Sequence[int], image_sizes,
+                  score_thresh: float = TTA_SCORE_THRESH):
+    """ptmi_tta_map_boxes: boxes (D,4) / scores (D) of all augmentations of a batch, concatenated in augmentation order ->
+    mapped + clipped boxes (D,4), keys (D) (score of a candidate, -inf otherwise), img_max (nimg,), img_count (nimg,) int32.
+    aug_rows / aug_counts: see _tta_tables; image_sizes: the original (H, W) of every image.  No host read."""
+    return _tta_map(boxes, scores, _tta_tables(aug_rows, aug_counts, image_sizes, scores.numel()), image_sizes, score_thresh)
+
+
+def _tta_map(boxes, scores, tables, image_sizes, score_thresh):
+    boxes, scores = _chk(boxes.contiguous()), _chk(scores.contiguous())
+    d, nimg, dev = scores.numel(), len(image_sizes), boxes.device
+    assert boxes.shape == (d, 4)
+    offs, meta, fact, _ = tables
+    out = torch.empty((d, 4), dtype=F32, device=dev)
+    keys = torch.empty(d, dtype=F32, device=dev)
+    img_max = torch.empty(nimg, dtype=F32, device=dev)
+    img_cnt = torch.empty(nimg, dtype=torch.int32, device=dev)
+    offs_d, meta_d = dev_i32(offs, dev), dev_i32(meta, dev)
+    fact_d = torch.tensor(fact, dtype=F32).pin_memory().to(dev, non_blocking=True)
+    _lib.call("ptmi_tta_map_boxes", _ptr(boxes), _ptr(scores), _ptr(offs_d), _ptr(meta_d), _ptr(fact_d),
+              _ptr(dev_sizes_hw(image_sizes, dev)), _ptr(out), _ptr(keys), _ptr(img_max), _ptr(img_cnt), d, len(meta), nimg,
+              float(score_thresh), _stream())
+    return out, keys, img_max, img_cnt
+
+
+def tta_nms_boxes(boxes, classes, order, seg_offsets, img_max, max_count: int) -> torch.Tensor:
+    """ptmi_tta_nms_boxes: the mapped boxes in sorted order per image segment + class * (img_max + 1), fp32."""
+    out = torch.empty((boxes.shape[0], 4), dtype=F32, device=boxes.device)
+    _lib.call("ptmi_tta_nms_boxes", _ptr(_chk(boxes)), _ptr(_chk(classes, torch.int64)), _ptr(_chk(order, torch.int32)),
+              _ptr(_chk(seg_offsets, torch.int32)), _ptr(_chk(img_max)), seg_offsets.numel() - 1, int(max_count), _ptr(out),
+              _stream())
+    return out
+
+
+def tta_merge(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, aug_rows, aug_counts: Sequence[int],
+              image_sizes, nms_thresh: float, max_det: int, score_thresh: float = TTA_SCORE_THRESH):
+    """D2 0.5 GeneralizedRCNNWithTTA._inverse_boxes + _merge_detections (plain fast_rcnn_inference_single_image) for all
+    images of a batch at once: the detections of every augmentation -- boxes (D,4), scores (D), classes (D) int64 in
+    augmented-image coordinates, concatenated in augmentation order, augmentations grouped by image -- are mapped back, filtered,
+    sorted per image (ties: position in the concatenation), passed through batched_nms at `nms_thresh`, and the first `max_det`
+    kept (negative: all).  Returns one (boxes (k,4), scores (k,), classes (k,)) per image.
+    Four entry points whatever the number of augmentations or detections (map, sort, class offsets, NMS) and ONE device->host
+    read, the kept counts.  An image with more detections than the single-pass bitmask NMS holds is a ValueError before any
+    launch.  (D2's batched_nms leaves the class-offset trick at 40 000 boxes for one NMS per class; this merge keeps the
+    offsets at every size -- the same pairs are compared either way.)"""
+    from .modeling.roi_heads import NMS_SEGMENT_MAX
+    nimg, dev = len(image_sizes), boxes.device
+    d = scores.numel()
+    tables = _tta_tables(aug_rows, aug_counts, image_sizes, d)
+    lengths = tables[3]
+    cap = max(lengths)
+    if cap > NMS_SEGMENT_MAX:
+        raise ValueError(f"TEST.AUG: {cap} detections of one image over all augmentations exceed the {NMS_SEGMENT_MAX} the "
+                         "single-pass bitmask NMS holds; lower TEST.DETECTIONS_PER_IMAGE or use fewer TEST.AUG.MIN_SIZES")
+    classes = _chk(classes.contiguous(), torch.int64)
+    if tuple(boxes.shape) != (d, 4) or classes.numel() != d:
+        raise ValueError(f"tta_merge: {d} scores, boxes {tuple(boxes.shape)}, {classes.numel()} classes")
+    if d == 0:
+        return [(torch.empty((0, 4), dtype=F32, device=dev), torch.empty(0, dtype=F32, device=dev),
+                 torch.empty(0, dtype=torch.int64, device=dev)) for _ in range(nimg)]
+    mapped, keys, img_max, img_cnt = _tta_map(boxes, scores, tables, image_sizes, score_thresh)
+    seg_h = [0]
+    for n in lengths:
+        seg_h.append(seg_h[-1] + n)
+    seg = dev_i32(seg_h, dev)
+    srt, order = segsort_desc(keys, seg, max_len=cap, lengths=lengths)
+    nms_boxes = tta_nms_boxes(mapped, classes, order, seg, img_max, cap)
+    max_keep = min(max_det, cap) if max_det >= 0 else cap
+    keep, kcnt = nms_batched(nms_boxes, seg, cap, float(nms_thresh), max(int(max_keep), 1), seg_counts=img_cnt)
+    kc = [min(k, max_keep) for k in kcnt.cpu().tolist()]                  # the one sync
+    first = seg[:-1].long()
+    keep_g = keep.long() + first.unsqueeze(1)                              # position in the sorted concatenation
+    out = []
+    for i in range(nimg):
+        pos = keep_g[i, :kc[i]]
+        src = first[i] + order[pos].long()
+        out.append((mapped[src], srt[pos], classes[src]))
+    return out
+
+
 def roi_class_seg_offsets(counts: Sequence[int], k: int) -> list:
     """Host list of the nimg * k + 1 offsets of the class-major layout of ROI inference by class (include/ptmi355.h): segment
     img * k + c = the counts[img] entries of class c of image img, starting at k * roff[img] + c * counts[img]."""

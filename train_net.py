@@ -98,6 +98,10 @@ def main():
     if args.eval_only and not args.synthetic:
         # reference train_net.py:60-75: evaluate the STUDENT of the loaded ensemble on cfg.DATASETS.TEST
         res = PTrainer.test(cfg, trainer.model)
+        if cfg.TEST.AUG.ENABLED:                               # D2 tools/train_net.py: the TTA results ride along as *_TTA
+            res_tta = PTrainer.test_with_TTA(cfg, trainer.model)
+            if res is not None and res_tta is not None:
+                res.update(res_tta)
         if rank == 0:
             print(res, flush=True)
         return
