@@ -691,6 +691,38 @@ int ptmi_clip_sgd_step_seg(float* p, const float* g, float* buf, int64_t n, cons
                            const int64_t* chunks, int C, const float* sumsq, float clip_norm, int clip_type,
                            float clip_value, const float* seg_norm, float lr, float momentum, float weight_decay,
                            int first, ptmi_stream_t s);
+/* ptmi_clip_sgd_step_seg with the weight decay of every segment read from the device table seg_wd[S] (D2's
+ * SOLVER.WEIGHT_DECAY_NORM: norm parameters decay at their own rate), and one more clip_type, 2 ("none"): g' = g*s + wd*p,
+ * clip_value and seg_norm unused -- a run without SOLVER.CLIP_GRADIENTS.  Same kernel body as the two entries above: with a
+ * constant table the result is bit-identical to ptmi_clip_sgd_step_seg, with clip_type 2 and a constant table to
+ * ptmi_clip_sgd_step. */
+int ptmi_clip_sgd_step_seg_wd(float* p, const float* g, float* buf, int64_t n, const int64_t* seg_off, int S,
+                              const int64_t* chunks, int C, const float* sumsq, float clip_norm, int clip_type,
+                              float clip_value, const float* seg_norm, float lr, float momentum, const float* seg_wd,
+                              int first, ptmi_stream_t s);
+
+/* ------------------------------------------------------------------ GroupNorm (+ ReLU) (csrc/groupnorm.hip)
+ * MODEL.VGG.NORM "GN": D2 get_norm("GN", C) = torch.nn.GroupNorm(32, C) behind the convolution's bias, F.relu_ behind it.
+ * z, y, dy, dz are (n, c, hw) fp32 NCHW maps; group (i, g) is the contiguous run of L = (c / groups) * hw floats at
+ * (i * groups + g) * L.  mean and BIASED variance over the run; y = (z - mean) * rsqrt(var + eps) * gamma[ch] + beta[ch], then
+ * max(y, 0) if relu.  mean_rstd: n * groups * 2 floats (mean, rstd per group), written by fwd and read by bwd.
+ * Sums: every run (fwd) and every channel plane (bwd) is cut into pieces of PTMI_GN_CHUNK floats, one workgroup each; element j
+ * of a piece always goes to thread (j / 4) % 256, whatever the address (16-byte loads where the piece starts on a 16-byte
+ * boundary, dwords otherwise), and threads, waves and pieces are combined in one fixed order -- pieces in double precision, as
+ * (count, mean, M2) by the parallel-variance formula in fwd.  No atomics: the bits depend on the values and the shape alone.
+ * No lane reads or writes outside its run / plane.  ws: ptmi_gn_ws_bytes bytes, 256-byte aligned.
+ * n == 0 or hw == 0: nothing is launched, 0 is returned.  c % groups != 0, a null pointer, or more than 2^31 - 1 pieces: < 0. */
+#define PTMI_GN_CHUNK 4096
+int ptmi_gn_chunk(void);
+int64_t ptmi_gn_ws_bytes(int n, int c, int64_t hw, int groups);
+int ptmi_gn_relu_fwd(const float* z, const float* gamma, const float* beta, float* y, float* mean_rstd, int n, int c,
+                     int64_t hw, int groups, float eps, int relu, void* ws, ptmi_stream_t s);
+/* g = dy * (y > 0) (relu) or dy; per plane A = sum g, B = sum g * xhat (xhat recomputed from z, mean, rstd);
+ * dbeta[ch] = sum_i A, dgamma[ch] = sum_i B (WRITTEN, not accumulated); s1 = sum_{ch in g} gamma A, s2 = sum gamma B;
+ * dz = rstd * (g * gamma - (s1 + xhat * s2) / L).  y may be NULL when relu == 0. */
+int ptmi_gn_relu_bwd(const float* dy, const float* y, const float* z, const float* gamma, const float* mean_rstd,
+                     float* dz, float* dgamma, float* dbeta, int n, int c, int64_t hw, int groups, int relu, void* ws,
+                     ptmi_stream_t s);
 
 /* ------------------------------------------------------------------ anomaly mode (csrc/anomaly.hip)
  * PTrainer(detect_anomaly=True); the reference runs every step under torch.autograd.set_detect_anomaly (trainer.py:167).

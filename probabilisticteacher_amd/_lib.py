@@ -151,6 +151,11 @@ SIGNATURES = {
     "ptmi_scale_by_clip": (_i, [_vp, _i64, _vp, _f, _vp]),
     "ptmi_seg_gradnorm": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i, _vp, _f, _i, _vp, _vp, _vp]),
     "ptmi_clip_sgd_step_seg": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _f, _i, _f, _vp, _f, _f, _f, _i, _vp]),
+    "ptmi_clip_sgd_step_seg_wd": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _f, _i, _f, _vp, _f, _f, _vp, _i, _vp]),
+    "ptmi_gn_chunk": (_i, []),
+    "ptmi_gn_ws_bytes": (_i64, [_i, _i, _i64, _i]),
+    "ptmi_gn_relu_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _f, _i, _vp, _vp]),
+    "ptmi_gn_relu_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp]),
     "ptmi_nonfinite_scan": (_i, [_vp, _i64, _i, _vp, _vp, _i, _i, _vp]),
     "ptmi_seg_nonfinite": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp]),
     "ptmi_preprocess_image": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp]),

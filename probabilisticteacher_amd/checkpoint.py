@@ -17,7 +17,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from .solver import lr_at, scheduler_state
+from .solver import lr_at, scheduler_state, segment_weight_decay
 
 IncompatibleKeys = namedtuple("IncompatibleKeys", ["missing_keys", "unexpected_keys", "incorrect_shapes"])
 
@@ -35,8 +35,10 @@ def optimizer_state_dict(trainer) -> Dict:
     # the file holds the learning rate of the NEXT iteration to run
     lr = lr_at(trainer.cfg, trainer.iter)
     groups, state = [], {}
+    # D2 get_default_optimizer_params: the groups of norm parameters carry SOLVER.WEIGHT_DECAY_NORM
+    decay = segment_weight_decay(trainer.cfg, trainer.model, names)
     for i, n in enumerate(names):
-        groups.append({"lr": lr, "momentum": S.MOMENTUM, "dampening": 0, "weight_decay": S.WEIGHT_DECAY,
+        groups.append({"lr": lr, "momentum": S.MOMENTUM, "dampening": 0, "weight_decay": decay[i],
                        "nesterov": bool(S.NESTEROV), "initial_lr": S.BASE_LR, "params": [i]})
         if not trainer._first_step:                    # torch creates momentum_buffer at the first step()
             off, k = trainer.student.index[n]

@@ -359,14 +359,15 @@ __global__ __launch_bounds__(256) void seg_gradnorm_final_kernel(const float* __
 }
 
 // clip_sgd_kernel's update with the per-parameter clip between the global scale and the weight decay.
-// NORM = 0: clamp(g s, -v, v) (NaN kept, as torch.clamp);  NORM = 1: g s c, c = min(v / (seg_norm + 1e-6), 1).
+// NORM = 0: clamp(g s, -v, v) (NaN kept, as torch.clamp);  NORM = 1: g s c, c = min(v / (seg_norm + 1e-6), 1);  NORM = 2: no
+// per-parameter clip (g s, clip_sgd_kernel's own expression).
 template <int NORM>
 __device__ __forceinline__ void clip_sgd_seg_elem(float& pv, float gv, float& bv, float sc, float cv, float lr, float mu,
                                                   float wd, int first)
 {
     gv *= sc;
-    if (NORM) gv *= cv;
-    else gv = gv < -cv ? -cv : (gv > cv ? cv : gv);
+    if (NORM == 1) gv *= cv;
+    else if (NORM == 0) gv = gv < -cv ? -cv : (gv > cv ? cv : gv);
     gv = gv + wd * pv;
     bv = first ? gv : mu * bv + gv;
     pv = pv - lr * bv;
@@ -374,20 +375,23 @@ __device__ __forceinline__ void clip_sgd_seg_elem(float& pv, float gv, float& bv
 
 // g is read only.  16-B accesses where p, g and buf sit at the same offset within 16 B (a scalar head up to that boundary, a
 // scalar tail); one dword per lane otherwise.  Elementwise: the path changes no bit of the result.
-template <int NORM>
+// SEGWD: the weight decay of the chunk's segment comes from the device table seg_wd[S] (ptmi_clip_sgd_step_seg_wd) instead of
+// the launch argument.
+template <int NORM, bool SEGWD>
 __global__ __launch_bounds__(256) void clip_sgd_seg_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                            float* __restrict__ buf, int64_t n,
                                                            const int64_t* __restrict__ seg_off, int S,
                                                            const int64_t* __restrict__ chunks,
                                                            const float* __restrict__ sumsq, float clip, float clip_value,
                                                            const float* __restrict__ seg_norm, float lr, float mu,
-                                                           float wd, int first)
+                                                           float wd, const float* __restrict__ seg_wd, int first)
 {
     int64_t a, e;
     int seg;
     if (!seg_chunk_range(seg_off, S, chunks, n, a, e, seg)) return;
+    if (SEGWD) wd = seg_wd[seg];
     const float sc = clip / fmaxf(sqrtf(sumsq[0]), clip);
-    const float cv = NORM ? fminf(clip_value / (seg_norm[seg] + 1e-6f), 1.f) : clip_value;
+    const float cv = NORM == 1 ? fminf(clip_value / (seg_norm[seg] + 1e-6f), 1.f) : clip_value;
     float* pp = p + a;
     const float* gp = g + a;
     float* bp = buf + a;
@@ -605,13 +609,39 @@ int ptmi_clip_sgd_step_seg(float* p, const float* g, float* buf, int64_t n, cons
     if (n == 0 || S == 0) return 0;
     PTMI_CHECK_ARG(p && g && buf && seg_off && chunks && sumsq && C > 0 && (clip_type == 0 || (clip_type == 1 && seg_norm)) &&
                    clip_value > 0.f, "clip_sgd_step_seg: bad args");
+    const float* no_table = nullptr;
     if (clip_type == 1)
-        hipLaunchKernelGGL(clip_sgd_seg_kernel<1>, dim3((unsigned)C), dim3(256), 0, (hipStream_t)s, p, g, buf, n, seg_off, S,
-                           chunks, sumsq, clip_norm, clip_value, seg_norm, lr, momentum, weight_decay, first);
+        hipLaunchKernelGGL((clip_sgd_seg_kernel<1, false>), dim3((unsigned)C), dim3(256), 0, (hipStream_t)s, p, g, buf, n, seg_off,
+                           S, chunks, sumsq, clip_norm, clip_value, seg_norm, lr, momentum, weight_decay, no_table, first);
     else
-        hipLaunchKernelGGL(clip_sgd_seg_kernel<0>, dim3((unsigned)C), dim3(256), 0, (hipStream_t)s, p, g, buf, n, seg_off, S,
-                           chunks, sumsq, clip_norm, clip_value, seg_norm, lr, momentum, weight_decay, first);
+        hipLaunchKernelGGL((clip_sgd_seg_kernel<0, false>), dim3((unsigned)C), dim3(256), 0, (hipStream_t)s, p, g, buf, n, seg_off,
+                           S, chunks, sumsq, clip_norm, clip_value, seg_norm, lr, momentum, weight_decay, no_table, first);
     PTMI_LAUNCH_CHECK("clip_sgd_step_seg");
+    return 0;
+}
+
+int ptmi_clip_sgd_step_seg_wd(float* p, const float* g, float* buf, int64_t n, const int64_t* seg_off, int S,
+                              const int64_t* chunks, int C, const float* sumsq, float clip_norm, int clip_type,
+                              float clip_value, const float* seg_norm, float lr, float momentum, const float* seg_wd,
+                              int first, ptmi_stream_t s)
+{
+    PTMI_CHECK_ARG(n >= 0 && S >= 0 && C >= 0, "clip_sgd_step_seg_wd: negative length");
+    if (n == 0 || S == 0) return 0;
+    PTMI_CHECK_ARG(p && g && buf && seg_off && chunks && sumsq && seg_wd && C > 0, "clip_sgd_step_seg_wd: bad args");
+    PTMI_CHECK_ARG(clip_type == 2 || (clip_value > 0.f && (clip_type == 0 || (clip_type == 1 && seg_norm))),
+                   "clip_sgd_step_seg_wd: clip type %d (0 value, 1 norm with segment norms, 2 none), clip value %g", clip_type,
+                   (double)clip_value);
+    const dim3 grid((unsigned)C), block(256);
+    if (clip_type == 1)
+        hipLaunchKernelGGL((clip_sgd_seg_kernel<1, true>), grid, block, 0, (hipStream_t)s, p, g, buf, n, seg_off, S, chunks, sumsq,
+                           clip_norm, clip_value, seg_norm, lr, momentum, 0.f, seg_wd, first);
+    else if (clip_type == 0)
+        hipLaunchKernelGGL((clip_sgd_seg_kernel<0, true>), grid, block, 0, (hipStream_t)s, p, g, buf, n, seg_off, S, chunks, sumsq,
+                           clip_norm, clip_value, seg_norm, lr, momentum, 0.f, seg_wd, first);
+    else
+        hipLaunchKernelGGL((clip_sgd_seg_kernel<2, true>), grid, block, 0, (hipStream_t)s, p, g, buf, n, seg_off, S, chunks, sumsq,
+                           clip_norm, clip_value, seg_norm, lr, momentum, 0.f, seg_wd, first);
+    PTMI_LAUNCH_CHECK("clip_sgd_step_seg_wd");
     return 0;
 }
 

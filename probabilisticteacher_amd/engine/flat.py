@@ -86,6 +86,13 @@ def segment_offsets(fp: FlatParams) -> List[int]:
     return offs
 
 
+def segment_weight_decays(fp: FlatParams, cfg, model: nn.Module) -> List[float]:
+    """The weight decay of every segment of `segment_offsets(fp)`, in its order: SOLVER.WEIGHT_DECAY_NORM for the parameters of
+    norm modules, SOLVER.WEIGHT_DECAY for all others (D2 get_default_optimizer_params; solver.segment_weight_decay)."""
+    from ..solver import segment_weight_decay
+    return segment_weight_decay(cfg, model, [n for n, p in fp.params.items() if p.requires_grad])
+
+
 def segment_chunks(offsets: List[int], chunk: int) -> Tuple[List[Tuple[int, int]], List[int]]:
     """Cut the segments into pieces of at most `chunk` elements, one workgroup each in the per-parameter clipping kernels
     (include/ptmi355.h): ([(start, segment), ...], first chunk of every segment + the chunk count).  An empty segment owns

@@ -19,7 +19,7 @@ from ..modeling import EnsembleTSModel, build_model, sampling
 from ..modeling import statistics as step_statistics
 from ..structures import Boxes, FreeInstances
 from ..solver import check_optimizer_options, clip_gradients_options, lr_at
-from .flat import BucketedGradReducer, FlatParams, broadcast_, segment_offsets
+from .flat import BucketedGradReducer, FlatParams, broadcast_, segment_offsets, segment_weight_decays
 
 
 class PTrainer:
@@ -76,6 +76,15 @@ class PTrainer:
         self._clip_gradients = clip_gradients_options(cfg)
         self._segments = (ops.SegmentTable(segment_offsets(self.student), self.student.flat.device)
                           if self._clip_gradients is not None else None)
+        # SOLVER.WEIGHT_DECAY_NORM (D2 get_default_optimizer_params): one weight decay per segment.  While every trainable segment
+        # has the same one -- no norm parameters, or WEIGHT_DECAY_NORM == WEIGHT_DECAY -- the step calls the entries it always
+        # called; otherwise the table goes to the device once and ops.clip_sgd_step_seg_wd reads it
+        self.segment_wd = segment_weight_decays(self.student, cfg, self.model)
+        self._seg_wd, self._wd_segments = None, None
+        if len(set(self.segment_wd)) > 1:
+            self._wd_segments = (self._segments if self._segments is not None else
+                                 ops.SegmentTable(segment_offsets(self.student), self.student.flat.device))
+            self._seg_wd = torch.tensor(self.segment_wd, dtype=torch.float32).to(self.student.flat.device)
         # gradient exchange overlapped with backward: 16 MB buckets from the tail of the flat buffer (box head first)
         self.reducer = BucketedGradReducer(self.student, self.world_size, bucket_elems=4 * 1024 * 1024,
                                            force=force_grad_reducer, mode=grad_reduce)
@@ -95,7 +104,7 @@ class PTrainer:
         # SOLVER.CLIP_GRADIENTS when it is enabled)
         self._anomaly, self._anomaly_segments = None, None
         if detect_anomaly:
-            self._anomaly_segments = (self._segments if self._segments is not None else
+            self._anomaly_segments = (self._segments or self._wd_segments or
                                       ops.SegmentTable(segment_offsets(self.student), self.student.flat.device))
             self._anomaly = AnomalySink(self.student.flat.device, segments=self._anomaly_segments.S)
             self._anomaly_names = [n for n, p in self.student.params.items() if p.requires_grad]     # segment order
@@ -213,7 +222,12 @@ class PTrainer:
         g = self.student.grad
         ss = ops.sumsq(g)
         S = self.cfg.SOLVER
-        if self._clip_gradients is None:
+        if self._seg_wd is not None:
+            clip_type, clip_value, inf_norm = self._clip_gradients or ("none", 0.0, False)
+            norms = ops.seg_gradnorm(g, self._wd_segments, ss, clip_norm, inf_norm) if clip_type == "norm" else None
+            ops.clip_sgd_step_seg_wd(self.student.trainable(), g, self.momentum_buf, self._wd_segments, ss, clip_norm, clip_type,
+                                     clip_value, norms, lr_at(self.cfg, self.iter), S.MOMENTUM, self._seg_wd, self._first_step)
+        elif self._clip_gradients is None:
             ops.clip_sgd_step(self.student.trainable(), g, self.momentum_buf, ss, clip_norm, lr_at(self.cfg, self.iter),
                               S.MOMENTUM, S.WEIGHT_DECAY, self._first_step)
         else:

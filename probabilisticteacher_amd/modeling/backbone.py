@@ -2,7 +2,13 @@
 
 Parameter names match the reference (`vgg_block{b}.0.conv{k}.{weight,bias}`, vgg.py:44,55,89-92) so its
 checkpoints / the vgg16_caffe.pth key map (vgg.py:130-145) apply unchanged.  Blocks 1..FREEZE_AT are frozen
-(vgg.py:175-180): they run without recording autograd state, so their activations are never kept."""
+(vgg.py:175-180): they run without recording autograd state, so their activations are never kept.
+
+MODEL.VGG.NORM (vgg.py:52,194 -> D2 get_norm): "None" (or "") builds the modules above; "GN" gives every convolution a `norm`
+child, torch.nn.GroupNorm(32, C) as D2 builds it (eps 1e-5, weight 1, bias 0), with the reference's state-dict layout
+`...conv{k}.weight, .bias, .norm.weight, .norm.bias`.  A layer is then relu(GN(conv(x) + b)) and the block runs layer by layer
+(ops.conv3x3 without ReLU, ops.group_norm_relu, ops.maxpool2x2): the statistics need the whole map, so the fused block node, the
+conv + pool epilogue and the frame skip belong to "None" only.  Every other value ("BN", "FrozenBN", "SyncBN", ...) raises."""
 import os
 from collections import namedtuple
 
@@ -23,26 +29,57 @@ VGG_CFGS = {
 _TORCHVISION_FEATURE_IDX = {16: [0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28]}
 
 
-class _ConvParams(nn.Module):
-    """Holds `weight` / `bias` of one 3x3 conv (c2_msra_fill init, vgg.py:61-63)."""
+NORM_KEY = "MODEL.VGG.NORM"
+NORMS = ("None", "GN")          # accepted values ("" counts as "None", as D2's get_norm treats it)
+GN_GROUPS, GN_EPS = 32, 1e-5    # D2 get_norm("GN", C) = nn.GroupNorm(32, C)
 
-    def __init__(self, cin, cout):
+
+def check_norm(norm) -> str:
+    """MODEL.VGG.NORM -> "" (no norm layer) or "GN"; anything else raises"""
+    if norm in ("", "None", None):
+        return ""
+    if norm == "GN":
+        return "GN"
+    raise ValueError(f"{NORM_KEY}={norm!r} is not implemented: accepted values are {', '.join(repr(v) for v in NORMS)} "
+                     "(BN, FrozenBN and SyncBN need running statistics this build does not have)")
+
+
+class _GroupNormParams(nn.Module):
+    """`weight` / `bias` of a conv's GroupNorm(32, C) child (ones / zeros, torch.nn.GroupNorm's own init)."""
+
+    def __init__(self, channels, groups=GN_GROUPS, eps=GN_EPS):
+        super().__init__()
+        if channels % groups:
+            raise ValueError(f"{NORM_KEY}='GN': {channels} channels do not divide into {groups} groups")
+        self.num_groups, self.num_channels, self.eps = groups, channels, eps
+        self.weight = nn.Parameter(torch.ones(channels))
+        self.bias = nn.Parameter(torch.zeros(channels))
+
+
+class _ConvParams(nn.Module):
+    """Holds `weight` / `bias` of one 3x3 conv (c2_msra_fill init, vgg.py:61-63) and, with a norm, its `norm` child -- set after
+    the conv's own parameters, as D2's Conv2d does, so that it follows them in the state dict and in the optimiser's numbering."""
+
+    def __init__(self, cin, cout, norm=""):
         super().__init__()
         self.weight = nn.Parameter(torch.empty(cout, cin, 3, 3))
         self.bias = nn.Parameter(torch.zeros(cout))
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
         self.out_channels = cout
+        if norm:
+            self.norm = _GroupNormParams(cout)
 
 
 class VGGBlock(nn.Module):
     """[conv3x3 + bias + ReLU] x k, then MaxPool(2,2) unless it is the last block (vgg.py:36-72)."""
 
-    def __init__(self, in_channels, channel_cfg, pool=True):
+    def __init__(self, in_channels, channel_cfg, pool=True, norm=""):
         super().__init__()
         self.pool = pool
+        self.norm = check_norm(norm)
         self.num_convs = len(channel_cfg)
         for i, cout in enumerate(channel_cfg):
-            setattr(self, f"conv{i + 1}", _ConvParams(in_channels, cout))
+            setattr(self, f"conv{i + 1}", _ConvParams(in_channels, cout, self.norm))
             in_channels = cout
         self.out_channels = in_channels
         self.stride = 2
@@ -54,6 +91,8 @@ class VGGBlock(nn.Module):
 
     def forward(self, x, frame=None):
         """frame: the batch's ops.FrameState at the block's input (shrink-pasted images), advanced layer by layer"""
+        if self.norm:
+            return self._forward_norm(x, frame)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return ops.vgg_block(x, self.pool, self.conv_params(), frame)     # one autograd node, fused backward chain
         fuse_pool = self.pool and not torch.is_grad_enabled()     # frozen block: full-res activation not needed
@@ -65,8 +104,21 @@ class VGGBlock(nn.Module):
                 x = ops.conv3x3(x, c.weight, c.bias, True, frame)
         return ops.maxpool2x2(x, frame) if self.pool else x
 
+    def _forward_norm(self, x, frame=None):
+        """MODEL.VGG.NORM "GN": relu(GN(conv(x) + b)) layer by layer, then the pool.  The group statistics run over the whole
+        map: no constant frame survives them, so the FrameState ends here.  A frozen block (it runs under no_grad) normalises
+        with its per-sample statistics like any other: D2's freeze converts BatchNorm only."""
+        ops._frame_end(frame)
+        for i in range(self.num_convs):
+            c = getattr(self, f"conv{i + 1}")
+            with ops.anomaly_scope(f"conv{i + 1}"):
+                x = ops.conv3x3(x, c.weight, c.bias, False)
+                with ops.anomaly_scope("norm"):
+                    x = ops.group_norm_relu(x, c.norm.weight, c.norm.bias, c.norm.num_groups, c.norm.eps, True)
+        return ops.maxpool2x2(x) if self.pool else x
+
     def freeze(self):
-        for p in self.parameters():
+        for p in self.parameters():         # (the norm children's parameters included, as CNNBlockBase.freeze)
             p.requires_grad = False
         return self
 
@@ -100,7 +152,7 @@ class VGG(nn.Module):
         own = self.state_dict()
         for idx, name in zip(_TORCHVISION_FEATURE_IDX[16], names):
             for suffix in ("weight", "bias"):
-                if f"{name}.{suffix}" in own:
+                if f"{name}.{suffix}" in own:           # (conv weights only: norm parameters keep their init, vgg.py:150 strict=False)
                     own[f"{name}.{suffix}"].copy_(sd[f"features.{idx}.{suffix}"])
 
     @property
@@ -142,6 +194,8 @@ class VGG(nn.Module):
     def forward(self, x, frame=None):
         """frame: ops.FrameState of a batch with shrink-pasted images (meta_arch.preprocess_image), or None"""
         if ops._native_bf16():
+            if any(getattr(self, name)[0].norm for name in self._names):
+                raise ValueError(f"{NORM_KEY}='GN' with SOLVER.AMP.ENABLED: the bf16-storage stack has no norm layer")
             return self._forward_p8(x)
         outputs = {}
         for name in self._names:
@@ -173,6 +227,7 @@ class VGG(nn.Module):
 @BACKBONE_REGISTRY.register()
 def build_vgg_backbone(cfg, input_shape):
     depth = cfg.MODEL.VGG.DEPTH
+    norm = check_norm(cfg.MODEL.VGG.NORM)
     out_features = cfg.MODEL.VGG.OUT_FEATURES
     layout = VGG_CFGS[depth]
     max_stage = max({"vgg_block1": 1, "vgg_block2": 2, "vgg_block3": 3, "vgg_block4": 4, "vgg_block5": 5}[f]
@@ -181,7 +236,7 @@ def build_vgg_backbone(cfg, input_shape):
     stages, start, cin = [], 0, input_shape.channels
     for s in range(max_stage):
         chans = layout[start:pools[s]]
-        stages.append(VGGBlock(cin, chans, pool=(s + 1 != 5)))
+        stages.append(VGGBlock(cin, chans, pool=(s + 1 != 5), norm=norm))
         cin, start = chans[-1], pools[s] + 1
     pretrain = cfg.MODEL.VGG.PRETRAIN if cfg.MODEL.VGG.PRETRAIN else ""
     return VGG(stages, out_features=out_features, pretrain=pretrain).freeze(cfg.MODEL.BACKBONE.FREEZE_AT)

@@ -201,6 +201,10 @@ class EnsembleTSModel(nn.Module):
 
 
 def build_model(cfg):
-    model = META_ARCH_REGISTRY.get(cfg.MODEL.META_ARCHITECTURE)(cfg)
+    from .backbone import check_norm
+    if check_norm(cfg.MODEL.VGG.NORM) and cfg.SOLVER.AMP.ENABLED:
+        raise ValueError("MODEL.VGG.NORM='GN' with SOLVER.AMP.ENABLED=True is not implemented: the bf16-storage backbone has no "
+                         "norm layer")
+    model =META_ARCH_REGISTRY.get(cfg.MODEL.META_ARCHITECTURE)(cfg)
     model.to(torch.device(cfg.MODEL.DEVICE))
     return model

@@ -850,6 +850,75 @@ def maxpool2x2(x, frame: Optional[FrameState] = None):
     return _MaxPool2x2.apply(x, frame)
 
 
+# ============================================================================ GroupNorm + ReLU (MODEL.VGG.NORM "GN")
+def gn_chunk() -> int:
+    """PTMI_GN_CHUNK: the piece size of the GroupNorm reductions (floats)"""
+    return int(_lib.load().ptmi_gn_chunk())
+
+
+def _gn_ws(n: int, c: int, hw: int, groups: int, device) -> torch.Tensor:
+    nbytes = int(_lib.load().ptmi_gn_ws_bytes(n, c, hw, groups))
+    if nbytes < 0:
+        raise _lib.PtmiError(f"ptmi_gn_ws_bytes failed: {_lib.load().ptmi_last_error().decode()}")
+    return _ws("groupnorm", nbytes, device)
+
+
+def _gn_bytes(n: int, c: int, hw: int, maps: int) -> float:
+    return 4.0 * (maps * n * c * hw + 2 * c)
+
+
+class _GroupNormReLU(torch.autograd.Function):
+    """relu(GroupNorm(groups, C)(z)): D2's Conv2d norm child + VGGBlock's F.relu_ (vgg.py:52,65-72).  Saves z, y and the group
+    statistics; backward recomputes xhat from z."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, groups: int, eps: float, relu: bool):
+        z = _chk(z.contiguous(), name="group norm input")
+        gamma, beta = _chk(gamma.contiguous(), name="group norm weight"), _chk(beta.contiguous(), name="group norm bias")
+        if z.dim() < 2:
+            raise ValueError(f"group_norm_relu: expected (N, C, ...) input, got {tuple(z.shape)}")
+        n, c = int(z.shape[0]), int(z.shape[1])
+        if groups <= 0 or c % groups:
+            raise ValueError(f"group_norm_relu: {c} channels do not divide into {groups} groups")
+        if gamma.numel() != c or beta.numel() != c:
+            raise ValueError(f"group_norm_relu: weight / bias of {gamma.numel()} / {beta.numel()} elements for {c} channels")
+        hw = z.numel() // (n * c) if n * c else 0
+        y = torch.empty_like(z)
+        stats = torch.empty((n * groups, 2), dtype=F32, device=z.device)
+        with _prof("gn_relu_fwd", 0.0, _gn_bytes(n, c, hw, 3)):         # z twice (statistics, apply), y once
+            _lib.call("ptmi_gn_relu_fwd", _ptr(z), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(stats), n, c, hw, groups, float(eps),
+                      int(bool(relu)), _ptr(_gn_ws(n, c, hw, groups, z.device)), _stream())
+        ctx.groups, ctx.relu = groups, bool(relu)
+        ctx.save_for_backward(z, y if relu else None, gamma, stats)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "group_norm_relu", (("y", y),))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, y, gamma, stats = ctx.saved_tensors
+        dy = _chk(dy.contiguous(), name="group norm grad")
+        n, c = int(z.shape[0]), int(z.shape[1])
+        hw = z.numel() // (n * c) if n * c else 0
+        dz = torch.empty_like(z)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+        if z.numel() == 0:
+            dgamma.zero_(), dbeta.zero_()
+        with _prof("gn_relu_bwd", 0.0, _gn_bytes(n, c, hw, 7 if ctx.relu else 5)):      # dy, z (and y) twice, dz once
+            _lib.call("ptmi_gn_relu_bwd", _ptr(dy), _ptr(y), _ptr(z), _ptr(gamma), _ptr(stats), _ptr(dz), _ptr(dgamma), _ptr(dbeta),
+                      n, c, hw, ctx.groups, int(ctx.relu), _ptr(_gn_ws(n, c, hw, ctx.groups, z.device)), _stream())
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "group_norm_relu", (("dgamma", dgamma), ("dbeta", dbeta), ("dz", dz)))
+        return dz, dgamma, dbeta, None, None, None
+
+
+def group_norm_relu(z, gamma, beta, groups: int = 32, eps: float = 1e-5, relu: bool = True):
+    """relu(group_norm(z, groups, gamma, beta, eps)) on (N, C, ...) fp32 maps (csrc/groupnorm.hip); fp32 only: the bf16-storage
+    stack has no norm layer"""
+    _no_native_bf16("ops.group_norm_relu")
+    return _GroupNormReLU.apply(z, gamma, beta, int(groups), float(eps), bool(relu))
+
+
 class _VGGBlock(torch.autograd.Function):
     """One VGG block = k x [conv3x3 + bias + ReLU] (+ MaxPool 2x2) as a single autograd node (vgg.py:65-72).
 
@@ -2149,6 +2218,27 @@ def clip_sgd_step_seg(p, g, buf, table: SegmentTable, sumsq_t, clip_norm, clip_t
               _ptr(table.chunks), table.C, _ptr(sumsq_t), float(clip_norm), int(clip_type == "norm"), float(clip_value),
               _ptr(seg_norm) if clip_type == "norm" else None, float(lr), float(momentum), float(weight_decay), int(first),
               _stream())
+
+
+_CLIP_TYPES = {"value": 0, "norm": 1, "none": 2}
+
+
+def clip_sgd_step_seg_wd(p, g, buf, table: SegmentTable, sumsq_t, clip_norm, clip_type: str, clip_value, seg_norm, lr, momentum,
+                         seg_wd: torch.Tensor, first: bool) -> None:
+    """clip_sgd_step_seg with one weight decay per segment, read from the device table seg_wd (fp32, table.S entries: D2's
+    SOLVER.WEIGHT_DECAY_NORM), and the clip type "none" (no SOLVER.CLIP_GRADIENTS; clip_value and seg_norm unused)."""
+    if clip_type not in _CLIP_TYPES:
+        raise ValueError(f"unknown clip type {clip_type!r}")
+    if clip_type == "norm" and seg_norm is None:
+        raise ValueError("clip type 'norm' needs the segment norms of seg_gradnorm")
+    table.check(p, g, buf)
+    _chk(seg_wd, name="seg_wd")
+    if seg_wd.numel() != table.S or seg_wd.device != table.table.device:
+        raise ValueError(f"seg_wd holds {seg_wd.numel()} values on {seg_wd.device} for {table.S} segments on {table.table.device}")
+    _lib.call("ptmi_clip_sgd_step_seg_wd", _ptr(p), _ptr(g), _ptr(buf), p.numel(), _ptr(table.seg_off), table.S,
+              _ptr(table.chunks), table.C, _ptr(sumsq_t), float(clip_norm), _CLIP_TYPES[clip_type],
+              float(clip_value) if clip_type != "none" else 0.0, _ptr(seg_norm) if clip_type == "norm" else None, float(lr),
+              float(momentum), _ptr(seg_wd), int(first), _stream())
 
 
 def _image_desc(rows, device) -> torch.Tensor:

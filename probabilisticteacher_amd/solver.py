@@ -51,8 +51,40 @@ def check_optimizer_options(cfg) -> None:
         raise ValueError("SOLVER.BIAS_LR_FACTOR != 1 is not implemented by the fused clip+SGD step")
     if float(S.WEIGHT_DECAY_BIAS) != float(S.WEIGHT_DECAY):
         raise ValueError("SOLVER.WEIGHT_DECAY_BIAS != SOLVER.WEIGHT_DECAY is not implemented by the fused clip+SGD step")
+    weight_decay_norm(cfg)
     clip_gradients_options(cfg)
-    lr_at(cfg, 0)          # unknown scheduler / warm-up names raise here, before the first step
+    lr_at(cfg, 0)         # unknown scheduler / warm-up names raise here, before the first step
+
+
+def weight_decay_norm(cfg) -> float:
+    """SOLVER.WEIGHT_DECAY_NORM (D2 get_default_optimizer_params: the weight decay of the parameters of norm modules; every
+    other parameter gets WEIGHT_DECAY): any finite value >= 0.  The fused step reads it from a per-segment table."""
+    try:
+        value = float(cfg.SOLVER.WEIGHT_DECAY_NORM)
+    except (TypeError, ValueError):
+        value = float("nan")
+    if not (math.isfinite(value) and value >= 0.0):
+        raise ValueError(f"SOLVER.WEIGHT_DECAY_NORM must be a finite number >= 0, got {cfg.SOLVER.WEIGHT_DECAY_NORM!r}")
+    return value
+
+
+def norm_parameter_names(model) -> set:
+    """Names (as `model.named_parameters()` gives them) of the parameters D2's get_default_optimizer_params treats as norm
+    parameters: those that belong to a norm module directly.  Here the norm modules are the `norm` children of the backbone's
+    convolutions (modeling/backbone.py: _GroupNormParams)."""
+    from .modeling.backbone import _GroupNormParams
+    names = set()
+    for mod_name, mod in model.named_modules():
+        if isinstance(mod, _GroupNormParams):
+            names.update(f"{mod_name}.{n}" if mod_name else n for n, _ in mod.named_parameters(recurse=False))
+    return names
+
+
+def segment_weight_decay(cfg, model, names) -> list:
+    """[weight decay of parameter `n` for n in names]: WEIGHT_DECAY_NORM for norm parameters, WEIGHT_DECAY for the others"""
+    norm = norm_parameter_names(model)
+    wd, wdn = float(cfg.SOLVER.WEIGHT_DECAY), weight_decay_norm(cfg)
+    return [wdn if n in norm else wd for n in names]
 
 
 def clip_gradients_options(cfg):

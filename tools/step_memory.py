@@ -1,6 +1,6 @@
 """How much device memory does the train step itself need?  What is left of the HBM is what `--image-cache-gb` may take.
 
-    python tools/step_memory.py [--amp] [--per-gpu-batch 16] [--steps 4] [--height 800] [--width 1333]
+    python tools/step_memory.py [--amp] [--norm GN] [--per-gpu-batch 16] [--steps 4] [--height 800] [--width 1333]
 
 The workload of bench.py (final_c2f.yaml, B labelled + B unlabelled synthetic images per step, teacher + student + EMA) WITHOUT
 bench.py's allocator warm-up pool, which would be the peak itself.  Prints one JSON line: the peaks of
@@ -21,6 +21,8 @@ from bench import synth_records  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--amp", action="store_true")
+    ap.add_argument("--norm", default="None", help="MODEL.VGG.NORM (GN keeps the pre-norm map z and the output y of every "
+                                                   "trainable layer until backward)")
     ap.add_argument("--per-gpu-batch", type=int, default=16)
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--height", type=int, default=800)
@@ -33,7 +35,7 @@ def main():
     B = args.per_gpu_batch
     cfg = setup_cfg(os.path.join(ROOT, "configs/pt/final_c2f.yaml"), [
         "MODEL.DEVICE", "cuda:0", "MODEL.VGG.PRETRAIN", "", "UNSUPNET.BURN_UP_STEP", 0, "SOLVER.IMG_PER_BATCH_LABEL", B,
-        "SOLVER.IMG_PER_BATCH_UNLABEL", B, "SOLVER.AMP.ENABLED", bool(args.amp)])
+        "SOLVER.IMG_PER_BATCH_UNLABEL", B, "SOLVER.AMP.ENABLED", bool(args.amp), "MODEL.VGG.NORM", args.norm])
     K = cfg.MODEL.ROI_HEADS.NUM_CLASSES
     torch.manual_seed(0)
     ratio_rng = random.Random(4321)
@@ -47,7 +49,7 @@ def main():
         trainer.run_step(batches[i % 2])
     torch.cuda.synchronize()
     gb = 1e-9
-    print(json.dumps({"amp": bool(args.amp), "per_gpu_batch": B, "steps": args.steps, "image": [args.height, args.width],
+    print(json.dumps({"amp": bool(args.amp), "norm": args.norm, "per_gpu_batch": B, "steps": args.steps, "image": [args.height, args.width],
                       "allocated_before_the_steps_gb": round(before * gb, 3),
                       "max_memory_allocated_gb": round(torch.cuda.max_memory_allocated() * gb, 3),
                       "max_memory_reserved_gb": round(torch.cuda.max_memory_reserved() * gb, 3),
