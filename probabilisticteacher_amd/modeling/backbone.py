@@ -85,7 +85,7 @@ class VGGBlock(nn.Module):
         self.stride = 2
 
     def conv_params(self):
-        """[w1, b1, w2, b2, ...]: what ops.vgg_block and p8.block take"""
+        """[w1, b1, w2, b2, ...]: what ops.vgg_block, p8.block and ops.frozen_block take"""
         convs = [getattr(self, f"conv{i + 1}") for i in range(self.num_convs)]
         return [p for c in convs for p in (c.weight, c.bias)]
 
@@ -95,14 +95,7 @@ class VGGBlock(nn.Module):
             return self._forward_norm(x, frame)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return ops.vgg_block(x, self.pool, self.conv_params(), frame)     # one autograd node, fused backward chain
-        fuse_pool = self.pool and not torch.is_grad_enabled()     # frozen block: full-res activation not needed
-        for i in range(self.num_convs):
-            c = getattr(self, f"conv{i + 1}")
-            if fuse_pool and i == self.num_convs - 1:
-                return ops.conv3x3_relu_pool_nograd(x, c.weight, c.bias, frame)
-            with ops.anomaly_scope(f"conv{i + 1}"):
-                x = ops.conv3x3(x, c.weight, c.bias, True, frame)
-        return ops.maxpool2x2(x, frame) if self.pool else x
+        return ops.frozen_block(ops.NCHW, x, *x.shape, self.pool, self.conv_params(), frame)     # layer by layer
 
     def _forward_norm(self, x, frame=None):
         """MODEL.VGG.NORM "GN": relu(GN(conv(x) + b)) layer by layer, then the pool.  The group statistics run over the whole
@@ -175,14 +168,8 @@ class VGG(nn.Module):
                 with ops.anomaly_scope(name + ".0"):
                     t = p8.block(t, n, c, h, w, blk.pool, params)
             else:
-                with torch.no_grad():
-                    for i in range(blk.num_convs):
-                        wt, b = params[2 * i], params[2 * i + 1]
-                        # a block without a backward pass: its last convolution pools in its epilogue (the full-resolution
-                        # activation is never written)
-                        epi = 4 if (blk.pool and i == blk.num_convs - 1) else 1
-                        t = p8.conv3x3_raw(t, p8.pack_weights(wt, 0), ops._chk(b.contiguous()), None, n, c, wt.shape[0], h, w, epi)
-                        c = wt.shape[0]
+                with torch.no_grad():       # (so the last convolution pools in its epilogue)
+                    t = ops.frozen_block(p8.P8, t, n, c, h, w, blk.pool, params)
             c = blk.out_channels
             if blk.pool:
                 h, w = h // 2, w // 2

@@ -116,7 +116,7 @@ class _prof:
 #                   map.  FC layers / 1x1 convolutions: ptmi_gemm_bf16 (fp32 tensors, operands rounded between LDS and the MFMA).
 #   "bf16_emulate"  the same numerics on the fp32 kernels: operands are rounded by a separate pass (x.to(bf16).to(f32))
 #                   and multiplied by v_mfma_f32_32x32x2_f32 -- a bf16 x bf16 product is exact in fp32 -- and what the storage
-#                   kernels store in bf16 (3x3-conv outputs and input gradients) is rounded by a pass as well (`_rnd_stored`;
+#                   kernels store in bf16 (3x3-conv outputs and input gradients) is rounded by a pass as well (`_rnd`;
 #                   it matters beyond the next layer's operand rounding: max-pool backward breaks TIES between rounded values
 #                   as autocast's bf16 pooling does), so the two modes differ in summation order only.  The native kernels
 #                   are tested against this mode.
@@ -263,11 +263,6 @@ def _rnd(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     if _OPERAND_ROUNDING != "bf16_emulate" or t is None:
         return t
     return t.to(torch.bfloat16).to(F32)
-
-
-def _rnd_stored(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    """bf16_emulate: a value the bf16-storage path would keep in bf16 (a 3x3-conv output or input gradient)"""
-    return _rnd(t)
 
 
 def _rnd_grad(t: torch.Tensor) -> torch.Tensor:
@@ -757,7 +752,7 @@ def conv3x3_relu_pool_nograd(x, weight, bias, frame: Optional[FrameState] = None
     x = _chk(_rnd(x).contiguous(), name="conv input")
     wp = conv3x3_pack(_chk(_rnd(weight).contiguous()), 0, 4, x.shape[-2:])
     frame_key = _frame_key(frame, weight.detach(), bias.detach())       # (detached: frozen as far as this call goes)
-    return _rnd_stored(_conv3x3_launch(x, wp, _chk(bias.contiguous()), None, weight.shape[0], 4, frame, frame_key))
+    return _rnd(_conv3x3_launch(x, wp, _chk(bias.contiguous()), None, weight.shape[0], 4, frame, frame_key))
 
 
 def relu_bwd(dy: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -769,50 +764,6 @@ def relu_bwd(dy: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     return dz
 
 
-class _Conv3x3(torch.autograd.Function):
-    """conv3x3 s1 p1 + bias (+ ReLU).  Replaces Conv2d + F.relu_ (vgg.py:45-53,66-69)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, relu: bool, frame=None):
-        frame_key = _frame_key(frame, weight, bias)
-        x = _chk(_rnd(x).contiguous(), name="conv input")
-        weight = _chk(_rnd(weight).contiguous(), name="conv weight")
-        bias = _chk(bias.contiguous(), name="conv bias")
-        wp = conv3x3_pack(weight, 0, 1 if relu else 0, x.shape[-2:])
-        y = _rnd_stored(conv3x3_raw(x, wp, bias, None, weight.shape[0], 1 if relu else 0, frame, frame_key))
-        ctx.relu = relu
-        ctx.save_for_backward(x, weight, y if relu else None)
-        if _ANOMALY is not None:
-            _anomaly_fwd(ctx, "conv3x3", (("y", y),))
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight, y = ctx.saved_tensors
-        dy = _chk(dy.contiguous(), name="conv grad")
-        dz = _rnd(relu_bwd(dy, y) if ctx.relu else dy)
-        n, cin, h, w = x.shape
-        cout = weight.shape[0]
-        dx = dw = db = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = conv3x3_wgrad(x, dz, cout)
-        if ctx.needs_input_grad[0]:
-            wpd = conv3x3_pack(weight, 1, 2, (h, w))
-            dx = _rnd_stored(conv3x3_raw(dz, wpd, None, None, cin, 2))
-        if _ANOMALY is not None:
-            _anomaly_bwd(ctx, "conv3x3", (("dw", dw), ("db", db), ("dx", dx)))
-        return dx, dw, db, None, None
-
-
-def conv3x3(x, weight, bias, relu: bool = True, frame: Optional[FrameState] = None):
-    """frame: the batch's FrameState at this layer's input (advanced to its output; dropped on paths that do not serve it)"""
-    if _native_bf16():
-        from . import p8
-        _frame_end(frame)
-        return p8.conv3x3_nchw(_chk(x.contiguous(), name="conv input"), weight, bias, relu)
-    return _Conv3x3.apply(x, weight, bias, relu, frame)
-
-
 # ============================================================================ max pool
 def _maxpool2x2_fwd(x, frame: Optional[FrameState] = None) -> torch.Tensor:
     """2x2 max pool of a checked map; a live FrameState passes the pool with it"""
@@ -822,6 +773,14 @@ def _maxpool2x2_fwd(x, frame: Optional[FrameState] = None) -> torch.Tensor:
         _lib.call("ptmi_maxpool2x2_fwd", _ptr(x), _ptr(y), n * c, h, w, _stream())
     frame_pool(frame, h, w)
     return y
+
+
+def _maxpool2x2_bwd(x, dy, relu_mask: bool) -> torch.Tensor:
+    """gradient of the pool's input x from that of its output; relu_mask: times (x > 0), the mask of the ReLU that produced x"""
+    n, c, h, w = x.shape
+    dx = torch.empty_like(x)
+    _lib.call("ptmi_maxpool2x2_bwd", _ptr(x), _ptr(_chk(dy)), _ptr(dx), n * c, h, w, int(relu_mask), _stream())
+    return dx
 
 
 class _MaxPool2x2(torch.autograd.Function):
@@ -836,10 +795,7 @@ class _MaxPool2x2(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        n, c, h, w = x.shape
-        dx = torch.empty_like(x)
-        _lib.call("ptmi_maxpool2x2_bwd", _ptr(x), _ptr(_chk(dy.contiguous())), _ptr(dx), n * c, h, w, 0, _stream())
+        dx = _maxpool2x2_bwd(ctx.saved_tensors[0], dy.contiguous(), False)
         if _ANOMALY is not None:
             _anomaly_bwd(ctx, "maxpool2x2", (("dx", dx),))
         return dx, None
@@ -919,67 +875,155 @@ def group_norm_relu(z, gamma, beta, groups: int = 32, eps: float = 1e-5, relu: b
     return _GroupNormReLU.apply(z, gamma, beta, int(groups), float(eps), bool(relu))
 
 
-class _VGGBlock(torch.autograd.Function):
-    """One VGG block = k x [conv3x3 + bias + ReLU] (+ MaxPool 2x2) as a single autograd node (vgg.py:65-72).
+# ============================================================================ the 3x3 stack: one block node, one conv node
+class NCHW:
+    """The fp32 (N, C, H, W) storage layout of the 3x3 stack, as _ConvBlock / _Conv / frozen_block see one (p8.P8 is the bf16 one):
+    how a layer is checked, packed, launched and reported.  Every method is handed the logical (n, c, h, w) of its operand -- an
+    fp32 tensor knows it, a P8 tensor does not."""
+    block_op, conv_op = "vgg_block", "conv3x3"          # anomaly op names.  ("bf16_emulate" rounding is the nodes' own: _rnd)
+    pack = staticmethod(conv3x3_pack)
+    relu_bwd = staticmethod(relu_bwd)
+
+    @staticmethod
+    def chk(t, n, c, h, w, name):
+        return _chk(t.contiguous(), name=name)
+
+    @staticmethod
+    def scan_shape(n, c, h, w):
+        return None
+
+    @staticmethod
+    def conv(x, wp, bias, mask_ref, n, cin, cout, h, w, epilogue, frame=None, frame_key=None):
+        return conv3x3_raw(x, wp, bias, mask_ref, cout, epilogue, frame, frame_key)
+
+    @staticmethod
+    def wgrad(x, dz, n, cin, cout, h, w):
+        return conv3x3_wgrad(x, dz, cout)
+
+    @staticmethod
+    def pool_fwd(x, n, c, h, w, frame=None):
+        return _maxpool2x2_fwd(x, frame)
+
+    @staticmethod
+    def pool_bwd(y, dout, n, c, h, w):
+        return _maxpool2x2_bwd(y, dout, True)
+
+    @staticmethod
+    def frozen_conv(x, n, cin, h, w, weight, bias, pooled: bool, frame, scope: str):
+        """the public entry points: the _Conv node (x may ask for a gradient; scans under `scope`) or the one launch of epilogue 4"""
+        if pooled:
+            return conv3x3_relu_pool_nograd(x, weight, bias, frame)
+        with anomaly_scope(scope):
+            return conv3x3(x, weight, bias, True, frame)
+
+    @staticmethod
+    def frozen_pool(x, n, c, h, w, frame=None):
+        return maxpool2x2(x, frame)        # (the autograd node: frozen_block may run with grad mode on)
+
+
+_WB = 8     # _ConvBlock / _Conv arguments: (x, layout, n, cin, h, w, pool or relu, frame), then the weights and biases
+
+
+class _Conv(torch.autograd.Function):
+    """conv3x3 s1 p1 + bias (+ ReLU) in the storage layout L.  Replaces Conv2d + F.relu_ (vgg.py:45-53,66-69)."""
+
+    @staticmethod
+    def forward(ctx, x, L, n, cin, h, w, relu, frame, weight, bias):
+        frame_key = _frame_key(frame, weight, bias)
+        x = L.chk(_rnd(x), n, cin, h, w, "conv input")
+        weight = _chk(_rnd(weight).contiguous(), name="conv weight")
+        bias = _chk(bias.contiguous(), name="conv bias")
+        cout, epilogue = weight.shape[0], 1 if relu else 0
+        y = _rnd(L.conv(x, L.pack(weight, 0, epilogue, (h, w)), bias, None, n, cin, cout, h, w, epilogue, frame, frame_key))
+        ctx.meta = (L, n, cin, h, w, relu)
+        ctx.save_for_backward(x, weight, y if relu else None)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, L.conv_op, (("y", y, None, L.scan_shape(n, cout, h, w)),))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L, n, cin, h, w, relu = ctx.meta
+        x, weight, y = ctx.saved_tensors
+        cout = weight.shape[0]
+        dy = L.chk(dy.contiguous(), n, cout, h, w, "conv grad")
+        dz = _rnd(L.relu_bwd(dy, y) if relu else dy)
+        dx = dw = db = None
+        if ctx.needs_input_grad[_WB] or ctx.needs_input_grad[_WB + 1]:
+            dw, db = L.wgrad(x, dz, n, cin, cout, h, w)
+        if ctx.needs_input_grad[0]:
+            dx = _rnd(L.conv(dz, L.pack(weight, 1, 2, (h, w)), None, None, n, cout, cin, h, w, 2))
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, L.conv_op, (("dw", dw), ("db", db), ("dx", dx, None, L.scan_shape(n, cin, h, w))))
+        return (dx,) + (None,) * (_WB - 1) + (dw, db)
+
+
+def conv3x3(x, weight, bias, relu: bool = True, frame: Optional[FrameState] = None):
+    """frame: the batch's FrameState at this layer's input (advanced to its output; dropped on paths that do not serve it)"""
+    if _native_bf16():
+        from . import p8
+        _frame_end(frame)
+        return p8.conv3x3_nchw(_chk(x.contiguous(), name="conv input"), weight, bias, relu)
+    return _Conv.apply(x, NCHW, *x.shape, relu, frame, weight, bias)
+
+
+class _ConvBlock(torch.autograd.Function):
+    """One VGG block = k x [conv3x3 + bias + ReLU] (+ MaxPool 2x2) in the storage layout L as a single autograd node
+    (vgg.py:65-72).
 
     The backward chain is fused: max-pool backward also applies the last ReLU's mask, and every dgrad launch
     applies the mask of the producing layer's ReLU in its epilogue (epilogue 3), so no separate ReLU-backward
-    passes (read dy + read y + write dz per layer) remain inside a block."""
+    passes (read dy + read y + write dz per layer) remain inside a block; one kernel per layer yields dW and db.  (The layout's
+    functions are bound once per call.)"""
 
     @staticmethod
-    def forward(ctx, x, pool: bool, frame, *wb):
-        k = len(wb) // 2
-        acts = [_chk(x.contiguous(), name="block input")]
-        ws = []
+    def forward(ctx, x, L, n, cin, h, w, pool, frame, *wb):
+        k, conv, pack, shape = len(wb) // 2, L.conv, L.pack, L.scan_shape
+        acts, ws, c = [L.chk(x, n, cin, h, w, "block input")], [], cin
         for j in range(k):
-            w, b = _chk(wb[2 * j].contiguous()), _chk(wb[2 * j + 1].contiguous())
-            ws.append(w)
-            acts.append(conv3x3_raw(acts[-1], conv3x3_pack(w, 0, 1, acts[-1].shape[-2:]), b, None, w.shape[0], 1, frame,
-                                    _frame_key(frame, wb[2 * j], wb[2 * j + 1])))
-        out = _maxpool2x2_fwd(acts[-1], frame) if pool else acts[-1]
-        ctx.k, ctx.pool = k, pool
+            wt, b = _chk(wb[2 * j].contiguous()), _chk(wb[2 * j + 1].contiguous())
+            ws.append(wt)
+            acts.append(conv(acts[-1], pack(wt, 0, 1, (h, w)), b, None, n, c, wt.shape[0], h, w, 1, frame,
+                             _frame_key(frame, wb[2 * j], wb[2 * j + 1])))
+            c = wt.shape[0]
+        out = L.pool_fwd(acts[-1], n, c, h, w, frame) if pool else acts[-1]
+        ctx.meta = (L, k, pool, n, h, w)
         ctx.save_for_backward(*acts, *ws)
         if _ANOMALY is not None:        # layer granularity: the node covers a whole block
-            _anomaly_fwd(ctx, "vgg_block", [("y", acts[j], f"conv{j}") for j in range(1, k + 1)] +
-                         ([("pooled", out)] if pool else []))
+            items = [("y", acts[j], f"conv{j}", shape(n, ws[j - 1].shape[0], h, w)) for j in range(1, k + 1)]
+            _anomaly_fwd(ctx, L.block_op, items + ([("pooled", out, None, shape(n, c, h // 2, w // 2))] if pool else []))
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        k = ctx.k
+        L, k, pool, n, h, w = ctx.meta
+        conv, pack, wgrad, shape = L.conv, L.pack, L.wgrad, L.scan_shape
         saved = ctx.saved_tensors
         acts, ws = saved[: k + 1], saved[k + 1:]
-        dout = _chk(dout.contiguous())
-        yk = acts[k]
-        if ctx.pool:
-            n, c, h, w = yk.shape
-            dz = torch.empty_like(yk)
-            _lib.call("ptmi_maxpool2x2_bwd", _ptr(yk), _ptr(dout), _ptr(dz), n * c, h, w, 1, _stream())
-        else:
-            dz = relu_bwd(dout, yk)
-        grads = [None] * (2 * k)
-        dx = None
-        seen = None if _ANOMALY is None else [("dz", dz, f"conv{k}")]
+        cout = ws[-1].shape[0]
+        dout = dout.contiguous()
+        dz = L.pool_bwd(acts[k], dout, n, cout, h, w) if pool else L.relu_bwd(dout, acts[k])
+        grads, dx = [None] * (2 * k), None
+        seen = None if _ANOMALY is None else [("dz", dz, f"conv{k}", shape(n, cout, h, w))]
         for j in range(k, 0, -1):
-            xin, w = acts[j - 1], ws[j - 1]
-            n, cin, h, wd = xin.shape
-            cout = w.shape[0]
-            if ctx.needs_input_grad[3 + 2 * (j - 1)] or ctx.needs_input_grad[4 + 2 * (j - 1)]:      # (x, pool, frame, w1, b1, ...)
-                dw, db = conv3x3_wgrad(xin, dz, cout)
+            xin, wt = acts[j - 1], ws[j - 1]
+            co, ci = wt.shape[0], wt.shape[1]
+            if ctx.needs_input_grad[_WB + 2 * (j - 1)] or ctx.needs_input_grad[_WB + 2 * (j - 1) + 1]:
+                dw, db = wgrad(xin, dz, n, ci, co, h, w)
                 grads[2 * (j - 1)], grads[2 * (j - 1) + 1] = dw, db
                 if seen is not None:
                     seen += [("dw", dw, f"conv{j}"), ("db", db, f"conv{j}")]
             if j > 1:
-                dz = conv3x3_raw(dz, conv3x3_pack(w, 1, 3, (h, wd)), None, xin, cin, 3)      # dgrad + ReLU mask of layer j-1
+                dz = conv(dz, pack(wt, 1, 3, (h, w)), None, xin, n, co, ci, h, w, 3)       # dgrad + ReLU mask of layer j - 1
                 if seen is not None:
-                    seen.append(("dz", dz, f"conv{j - 1}"))
+                    seen.append(("dz", dz, f"conv{j - 1}", shape(n, ci, h, w)))
             elif ctx.needs_input_grad[0]:
-                dx = conv3x3_raw(dz, conv3x3_pack(w, 1, 2, (h, wd)), None, None, cin, 2)
+                dx = conv(dz, pack(wt, 1, 2, (h, w)), None, None, n, co, ci, h, w, 2)
                 if seen is not None:
-                    seen.append(("dx", dx, "conv1"))
+                    seen.append(("dx", dx, "conv1", shape(n, ci, h, w)))
         if seen is not None:
-            _anomaly_bwd(ctx, "vgg_block", seen)
-        return (dx, None, None, *grads)
+            _anomaly_bwd(ctx, L.block_op, seen)
+        return (dx,) + (None,) * (_WB - 1) + tuple(grads)
 
 
 def vgg_block(x, pool: bool, params, frame: Optional[FrameState] = None):
@@ -993,7 +1037,18 @@ def vgg_block(x, pool: bool, params, frame: Optional[FrameState] = None):
         for j in range(len(params) // 2):
             x = conv3x3(x, params[2 * j], params[2 * j + 1], True)
         return maxpool2x2(x) if pool else x
-    return _VGGBlock.apply(x, pool, frame, *params)
+    return _ConvBlock.apply(x, NCHW, *x.shape, pool, frame, *params)
+
+
+def frozen_block(L, x, n, cin, h, w, pool: bool, params, frame: Optional[FrameState] = None):
+    """The block layer by layer, for a block whose parameters have no backward pass: conv + bias + ReLU per layer, then the pool.
+    With grad mode off the last convolution pools in its epilogue (4): the full-resolution activation is not needed.  What a
+    layer is differs by layout: NCHW the public entry points, which scan under the scope "conv{j}"; P8 raw launches."""
+    k, fuse_pool, layer = len(params) // 2, pool and not torch.is_grad_enabled(), L.frozen_conv
+    for j in range(k):
+        x = layer(x, n, cin, h, w, params[2 * j], params[2 * j + 1], fuse_pool and j == k - 1, frame, f"conv{j + 1}")
+        cin = params[2 * j].shape[0]
+    return L.frozen_pool(x, n, cin, h, w, frame) if pool and not fuse_pool else x
 
 
 # ============================================================================ GEMM family

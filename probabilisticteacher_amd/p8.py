@@ -186,62 +186,47 @@ class _FromNCHW(torch.autograd.Function):
         return to_nchw(dt.contiguous(), *ctx.meta)
 
 
-class _Block(torch.autograd.Function):
-    """k x [conv3x3 + bias + ReLU] (+ MaxPool 2x2) on P8 tensors as ONE autograd node (vgg.py:65-72): the counterpart of
-    ops._VGGBlock -- pool backward applies the last ReLU's mask, every dgrad launch the mask of the producing layer (epilogue 3),
-    weight + bias gradients come out of one kernel per layer."""
+class P8:
+    """The bf16-storage layout of the 3x3 stack for ops._ConvBlock / ops._Conv / ops.frozen_block (the counterpart of ops.NCHW).
+    No FrameState is served here: callers end it before they route to P8."""
+    block_op, conv_op = "p8_block", "p8_conv3x3"        # anomaly op names
+    wgrad = staticmethod(wgrad)
+    relu_bwd = staticmethod(relu_bwd)
 
     @staticmethod
-    def forward(ctx, x, n, cin, h, w, pool, *wb):
-        k = len(wb) // 2
-        acts, ws, c = [_chk(x, cin, n, h, w, "block input")], [], cin
-        for j in range(k):
-            wt, b = ops._chk(wb[2 * j].contiguous()), ops._chk(wb[2 * j + 1].contiguous())
-            ws.append(wt)
-            acts.append(conv3x3_raw(acts[-1], pack_weights(wt, 0), b, None, n, c, wt.shape[0], h, w, 1))
-            c = wt.shape[0]
-        out = maxpool_fwd(acts[-1], n, c, h, w) if pool else acts[-1]
-        ctx.meta = (k, pool, n, cin, h, w)
-        ctx.save_for_backward(*acts, *ws)
-        if ops._ANOMALY is not None:        # layer granularity: the node covers a whole block
-            ops._anomaly_fwd(ctx, "p8_block", [("y", acts[j], f"conv{j}", (n, ws[j - 1].shape[0], h, w)) for j in range(1, k + 1)] +
-                             ([("pooled", out, None, (n, c, h // 2, w // 2))] if pool else []))
-        return out
+    def chk(t, n, c, h, w, name):
+        return _chk(t, c, n, h, w, name)
 
     @staticmethod
-    def backward(ctx, dout):
-        k, pool, n, cin, h, w = ctx.meta
-        saved = ctx.saved_tensors
-        acts, ws = saved[: k + 1], saved[k + 1:]
-        cout = ws[-1].shape[0]
-        dout = dout.contiguous()
-        dz = maxpool_bwd(acts[k], dout, n, cout, h, w, True) if pool else relu_bwd(dout, acts[k])
-        grads = [None] * (2 * k)
-        dx = None
-        seen = None if ops._ANOMALY is None else [("dz", dz, f"conv{k}", (n, cout, h, w))]
-        for j in range(k, 0, -1):
-            xin, wt = acts[j - 1], ws[j - 1]
-            co, ci = wt.shape[0], wt.shape[1]
-            if ctx.needs_input_grad[6 + 2 * (j - 1)] or ctx.needs_input_grad[7 + 2 * (j - 1)]:
-                grads[2 * (j - 1)], grads[2 * (j - 1) + 1] = wgrad(xin, dz, n, ci, co, h, w)
-                if seen is not None:
-                    seen += [("dw", grads[2 * (j - 1)], f"conv{j}"), ("db", grads[2 * (j - 1) + 1], f"conv{j}")]
-            if j > 1:
-                dz = conv3x3_raw(dz, pack_weights(wt, 1), None, xin, n, co, ci, h, w, 3)       # dgrad + ReLU mask of layer j - 1
-                if seen is not None:
-                    seen.append(("dz", dz, f"conv{j - 1}", (n, ci, h, w)))
-            elif ctx.needs_input_grad[0]:
-                dx = conv3x3_raw(dz, pack_weights(wt, 1), None, None, n, co, ci, h, w, 2)
-                if seen is not None:
-                    seen.append(("dx", dx, "conv1", (n, ci, h, w)))
-        if seen is not None:
-            ops._anomaly_bwd(ctx, "p8_block", seen)
-        return (dx, None, None, None, None, None, *grads)
+    def scan_shape(n, c, h, w):
+        return (n, c, h, w)
+
+    @staticmethod
+    def pack(weight, mode, epilogue, hw):
+        return pack_weights(weight, mode)
+
+    @staticmethod
+    def conv(x, wp, bias, mask_ref, n, cin, cout, h, w, epilogue, frame=None, frame_key=None):
+        return conv3x3_raw(x, wp, bias, mask_ref, n, cin, cout, h, w, epilogue)
+
+    @staticmethod
+    def pool_fwd(x, n, c, h, w, frame=None):
+        return maxpool_fwd(x, n, c, h, w)
+    frozen_pool = pool_fwd      # (not reached from VGG._forward_p8: it runs frozen blocks under no_grad, where the last conv pools)
+
+    @staticmethod
+    def pool_bwd(y, dout, n, c, h, w):
+        return maxpool_bwd(y, dout, n, c, h, w, True)
+
+    @staticmethod
+    def frozen_conv(x, n, cin, h, w, weight, bias, pooled: bool, frame=None, scope=None):
+        return conv3x3_raw(x, pack_weights(weight, 0), ops._chk(bias.contiguous()), None, n, cin, weight.shape[0], h, w,
+                           4 if pooled else 1)
 
 
 def block(x: torch.Tensor, n: int, cin: int, h: int, w: int, pool: bool, params) -> torch.Tensor:
     """P8 in, P8 out.  params = [w1, b1, w2, b2, ...]"""
-    return _Block.apply(x, n, cin, h, w, pool, *params)
+    return ops._ConvBlock.apply(x, P8, n, cin, h, w, pool, None, *params)
 
 
 # ---------------------------------------------------------------------------- fp32-NCHW-facing entry points (ops routes here)
@@ -249,37 +234,8 @@ def conv3x3_nchw(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu
     """ops.conv3x3 in "bf16" mode: fp32 NCHW in and out, the convolution and its gradients on the P8 kernels"""
     n, cin, h, w = x.shape
     t = _FromNCHW.apply(x) if x.requires_grad else from_nchw(x)
-    y = _Conv.apply(t, n, cin, h, w, relu, weight, bias)
+    y = ops._Conv.apply(t, P8, n, cin, h, w, relu, None, weight, bias)
     return _ToNCHW.apply(y, n, weight.shape[0], h, w)
-
-
-class _Conv(torch.autograd.Function):
-    """one conv3x3 + bias (+ ReLU) on P8 tensors"""
-
-    @staticmethod
-    def forward(ctx, x, n, cin, h, w, relu, weight, bias):
-        weight, bias = ops._chk(weight.contiguous(), name="conv weight"), ops._chk(bias.contiguous(), name="conv bias")
-        y = conv3x3_raw(x, pack_weights(weight, 0), bias, None, n, cin, weight.shape[0], h, w, 1 if relu else 0)
-        ctx.meta = (n, cin, h, w, relu)
-        ctx.save_for_backward(x, weight, y if relu else None)
-        if ops._ANOMALY is not None:
-            ops._anomaly_fwd(ctx, "p8_conv3x3", (("y", y, None, (n, weight.shape[0], h, w)),))
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        n, cin, h, w, relu = ctx.meta
-        x, weight, y = ctx.saved_tensors
-        cout = weight.shape[0]
-        dz = relu_bwd(dy.contiguous(), y) if relu else dy.contiguous()
-        dx = dw = db = None
-        if ctx.needs_input_grad[6] or ctx.needs_input_grad[7]:
-            dw, db = wgrad(x, dz, n, cin, cout, h, w)
-        if ctx.needs_input_grad[0]:
-            dx = conv3x3_raw(dz, pack_weights(weight, 1), None, None, n, cout, cin, h, w, 2)
-        if ops._ANOMALY is not None:
-            ops._anomaly_bwd(ctx, "p8_conv3x3", (("dw", dw), ("db", db), ("dx", dx, None, (n, cin, h, w))))
-        return dx, None, None, None, None, None, dw, db
 
 
 def vgg_block_nchw(x: torch.Tensor, pool: bool, params) -> torch.Tensor:
@@ -293,9 +249,8 @@ def vgg_block_nchw(x: torch.Tensor, pool: bool, params) -> torch.Tensor:
 
 def conv3x3_relu_pool_nograd_nchw(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     n, cin, h, w = x.shape
-    cout = weight.shape[0]
-    y = conv3x3_raw(from_nchw(x), pack_weights(weight, 0), ops._chk(bias.contiguous()), None, n, cin, cout, h, w, 4)
-    return to_nchw(y, n, cout, h // 2, w // 2)
+    y = P8.frozen_conv(from_nchw(x), n, cin, h, w, weight, bias, True)
+    return to_nchw(y, n, weight.shape[0], h // 2, w // 2)
 
 
 # ============================================================================ bf16-storage GEMM (the box head's large Linear layer)
@@ -351,26 +306,34 @@ class _LinearP8(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        xt, weight, y = ctx.saved_tensors
-        r, k, n, relu, need_dx = ctx.meta
-        dy = ops._chk(dy.contiguous())
-        dz = ops.relu_bwd(dy, y) if relu else dy
-        dx = dw = db = None
-        if need_dx:                                        # dX = dZ W:  A = dZ (k = n), B = W^T (rows = input feature, k = n)
-            dx = gemm_nt(pack_matrix(dz, r, n, n, True), pack_matrix(weight, k, n, k, False), r, k, n, swapped=True)
-        if ctx.needs_input_grad[1]:                        # dW = dZ^T X:  A = dZ^T (rows n, k = r), B = X^T (rows = input feature, k = r)
-            dw = gemm_nt(pack_matrix(dz, n, r, n, False), xt, n, k, r)
-        if ctx.needs_input_grad[2]:                        # the bias gradient sums the values the GEMMs consumed (rounded)
-            db = ops.colsum(dz.to(BF16).to(F32))
+        dx, _, dw, db = _linear_bwd(ctx, dy, ctx.meta[4], ctx.needs_input_grad[1], ctx.needs_input_grad[2])
         if ops._ANOMALY is not None:
             ops._anomaly_bwd(ctx, "p8_linear", (("dx", dx), ("dw", dw), ("db", db)))
         return dx, dw, db, None, None
 
 
+def _linear_bwd(ctx, dy, need_dx: bool, need_dw: bool, need_db: bool, dx_to=None):
+    """(dX, dx_to(dX), dW, db) of the two nodes here from dY; ctx: saved tensors (xt, weight, y, ...), meta (r, k, n, relu, ...).
+    dx_to consumes dX before the dW GEMM is launched (_RoiAlignLinearP8: the ROIAlign backward)."""
+    xt, weight, y = ctx.saved_tensors[:3]
+    r, k, n, relu = ctx.meta[:4]
+    dy = ops._chk(dy.contiguous())
+    dz = ops.relu_bwd(dy, y) if relu else dy
+    dx = dfeat = dw = db = None
+    if need_dx:                                        # dX = dZ W:  A = dZ (k = n), B = W^T (rows = input feature, k = n)
+        dx = gemm_nt(pack_matrix(dz, r, n, n, True), pack_matrix(weight, k, n, k, False), r, k, n, swapped=True)
+        dfeat = dx_to(dx) if dx_to is not None else None
+    if need_dw:                                        # dW = dZ^T X:  A = dZ^T (rows n, k = r), B = X^T (rows = input feature, k = r)
+        dw = gemm_nt(pack_matrix(dz, n, r, n, False), xt, n, k, r)
+    if need_db:                                        # the bias gradient sums the values the GEMMs consumed (rounded)
+        db = ops.colsum(dz.to(BF16).to(F32))
+    return dx, dfeat, dw, db
+
+
 class _RoiAlignLinearP8(torch.autograd.Function):
     """ROIPooler -> flatten -> Linear (+ ReLU) of the box head (roi_heads.py:126-128 -> FastRCNNConvFCHead.fc1) as ONE node under
     SOLVER.AMP.ENABLED: the ROIAlign kernel writes the Linear layer's bf16 operands itself (no fp32 ROI-feature tensor, no pack passes
-    over it); backward = _LinearP8's three GEMMs, then the grouped ROIAlign backward on dX."""
+    over it); backward = _LinearP8's (_linear_bwd), with the grouped ROIAlign backward on dX."""
 
     @staticmethod
     def forward(ctx, feat, rois, img_offsets, pooled: int, scale: float, weight, bias, relu: bool, recording: bool = True):
@@ -388,18 +351,10 @@ class _RoiAlignLinearP8(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        xt, weight, y, rois, img_offsets = ctx.saved_tensors
-        r, k, n, relu, (n_img, c, h, w), pooled, scale = ctx.meta
-        dy = ops._chk(dy.contiguous())
-        dz = ops.relu_bwd(dy, y) if relu else dy
-        dfeat = dw = db = dx = None
-        if ctx.needs_input_grad[0]:
-            dx = gemm_nt(pack_matrix(dz, r, n, n, True), pack_matrix(weight, k, n, k, False), r, k, n, swapped=True)
-            dfeat = ops.roi_align_bwd_grouped(dx, rois, img_offsets, n_img, c, h, w, pooled, scale)
-        if ctx.needs_input_grad[5]:
-            dw = gemm_nt(pack_matrix(dz, n, r, n, False), xt, n, k, r)
-        if ctx.needs_input_grad[6]:
-            db = ops.colsum(dz.to(BF16).to(F32))
+        rois, img_offsets = ctx.saved_tensors[3:]
+        (n_img, c, h, w), pooled, scale = ctx.meta[4:]
+        dx, dfeat, dw, db = _linear_bwd(ctx, dy, ctx.needs_input_grad[0], ctx.needs_input_grad[5], ctx.needs_input_grad[6],
+                                        lambda dx: ops.roi_align_bwd_grouped(dx, rois, img_offsets, n_img, c, h, w, pooled, scale))
         if ops._ANOMALY is not None:
             ops._anomaly_bwd(ctx, "p8_roi_align_linear", (("dpooled", dx), ("dfeat", dfeat), ("dw", dw), ("db", db)))
         return dfeat, None, None, None, None, dw, db, None, None

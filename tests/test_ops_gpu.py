@@ -1051,8 +1051,8 @@ def test_conv3x3_bf16_native(ops, n, cin, cout, h, w, relu):
 
 @pytest.mark.parametrize("pool", [False, True])
 def test_vgg_block_bf16_native(ops, pool):
-    """The VGG block on the bf16-storage kernels (epilogues 1 / 3, P8 pool backward; p8._Block) against the same block run layer
-    by layer in "bf16_emulate" mode (separate rounding passes + the fp32 kernels), and the inference-only conv+ReLU+pool."""
+    """The VGG block on the bf16-storage kernels (epilogues 1 / 3, P8 pool backward; ops._ConvBlock in the p8.P8 layout) against the same
+    block run layer by layer in "bf16_emulate" mode (separate rounding passes + the fp32 kernels), and the inference-only conv+ReLU+pool."""
     gen = g(197)
     x = torch.randn(2, 16, 22, 37, generator=gen)
     ws = [torch.randn(24, 16, 3, 3, generator=gen) * 0.1, torch.randn(24, 24, 3, 3, generator=gen) * 0.08,
