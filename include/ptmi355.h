@@ -724,6 +724,35 @@ int ptmi_gn_relu_bwd(const float* dy, const float* y, const float* z, const floa
                      float* dz, float* dgamma, float* dbeta, int n, int c, int64_t hw, int groups, int relu, void* ws,
                      ptmi_stream_t s);
 
+/* ------------------------------------------------------------------ ROI mosaic (csrc/roi_mosaic.hip)
+ * MODEL.ROI_BOX_HEAD.NUM_CONV > 0 (D2 FastRCNNConvFCHead's conv layers): pooled ROIs (r, c, pooled, pooled) are packed into
+ * canvases so that the 3x3 kernels see ordinary maps.  p = pooled + 1, gx = max(1, 64 / p), S = gx * p: canvases are
+ * (ceil(r / gx^2), c, S, S); ROI i sits in canvas i / gx^2, cell row (i % gx^2) / gx, cell column i % gx, its data in the cell's
+ * first `pooled` rows and columns.  Row and column `pooled` of every cell (the gutter) and the cells past r hold exactly 0.0 in
+ * every tensor a convolution reads.  All entries: no sync, the passed stream only, r == 0 launches nothing and returns 0; the
+ * bits of every result depend on the values and the shape alone, not on the addresses (16-byte accesses where the canvas sits
+ * on a 16-byte boundary, dwords otherwise; no atomics).
+ * pack: x -> canvas, zeros written to gutters and empty cells (every canvas element is written).  unpack: canvas -> x, its
+ * backward (and pack is unpack's).  mask: out = in on the data pixels, 0.0 on gutters and empty cells; out != in (the saved
+ * output of the producing convolution stays as it is); its own backward. */
+int ptmi_roi_mosaic_pack(const float* x, float* canvas, int r, int c, int pooled, ptmi_stream_t s);
+int ptmi_roi_mosaic_unpack(const float* canvas, float* x, int r, int c, int pooled, ptmi_stream_t s);
+int ptmi_roi_mosaic_mask(const float* in, float* out, int r, int c, int pooled, ptmi_stream_t s);
+/* relu(GroupNorm(groups, c)(z)) per (ROI, group) over the data pixels of canvases: L = (c / groups) * pooled^2 values, mean and
+ * BIASED variance, one wave per (ROI, group) with the cell in registers (at most PTMI_ROI_MOSAIC_GN_MAX_CELL =
+ * (c / groups) * (pooled + 1)^2 floats): sum -> mean, corrected by the residual sum, then M2 about the mean.  y and dz get 0.0 on
+ * gutters and empty cells.  mean_rstd: r * groups * 2 floats.  bwd: g = dy * (y > 0); dz = rstd * (g * gamma - (s1 + xhat * s2) / L);
+ * dgamma / dbeta (WRITTEN) in two stages: per (canvas, channel) plane into ws (ptmi_roi_mosaic_gn_ws_bytes, 256-byte aligned),
+ * then canvases in canvas order in double. */
+#define PTMI_ROI_MOSAIC_GN_MAX_CELL 2048
+int ptmi_roi_mosaic_gn_max_cell(void);
+int64_t ptmi_roi_mosaic_gn_ws_bytes(int r, int c, int pooled, int groups);
+int ptmi_roi_mosaic_gn_relu_fwd(const float* z, const float* gamma, const float* beta, float* y, float* mean_rstd, int r, int c,
+                                int pooled, int groups, float eps, ptmi_stream_t s);
+int ptmi_roi_mosaic_gn_relu_bwd(const float* dy, const float* y, const float* z, const float* gamma, const float* mean_rstd,
+                                float* dz, float* dgamma, float* dbeta, int r, int c, int pooled, int groups, void* ws,
+                                ptmi_stream_t s);
+
 /* ------------------------------------------------------------------ anomaly mode (csrc/anomaly.hip)
  * PTrainer(detect_anomaly=True); the reference runs every step under torch.autograd.set_detect_anomaly (trainer.py:167).
  * Does a tensor hold a NaN or an infinity, and where is the first: x = n elements of dtype 0 (fp32) or 1 (bf16, 2-byte elements

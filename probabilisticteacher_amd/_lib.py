@@ -156,6 +156,13 @@ SIGNATURES = {
     "ptmi_gn_ws_bytes": (_i64, [_i, _i, _i64, _i]),
     "ptmi_gn_relu_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _f, _i, _vp, _vp]),
     "ptmi_gn_relu_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp]),
+    "ptmi_roi_mosaic_gn_max_cell": (_i, []),
+    "ptmi_roi_mosaic_pack": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ptmi_roi_mosaic_unpack": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ptmi_roi_mosaic_mask": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ptmi_roi_mosaic_gn_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "ptmi_roi_mosaic_gn_relu_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "ptmi_roi_mosaic_gn_relu_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ptmi_nonfinite_scan": (_i, [_vp, _i64, _i, _vp, _vp, _i, _i, _vp]),
     "ptmi_seg_nonfinite": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp]),
     "ptmi_preprocess_image": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp]),

@@ -205,6 +205,9 @@ def build_model(cfg):
     if check_norm(cfg.MODEL.VGG.NORM) and cfg.SOLVER.AMP.ENABLED:
         raise ValueError("MODEL.VGG.NORM='GN' with SOLVER.AMP.ENABLED=True is not implemented: the bf16-storage backbone has no "
                          "norm layer")
+    if cfg.MODEL.ROI_BOX_HEAD.NUM_CONV > 0 and cfg.SOLVER.AMP.ENABLED:
+        raise ValueError(f"MODEL.ROI_BOX_HEAD.NUM_CONV={cfg.MODEL.ROI_BOX_HEAD.NUM_CONV} with SOLVER.AMP.ENABLED=True is not "
+                         "implemented: the bf16-storage stack has no box-head conv layers")
     model =META_ARCH_REGISTRY.get(cfg.MODEL.META_ARCHITECTURE)(cfg)
     model.to(torch.device(cfg.MODEL.DEVICE))
     return model

@@ -92,16 +92,66 @@ class DeferredROIAlign:
         return ops.roi_align(self.feat, self.rois, self.output_size, self.scale, self.img_offsets)
 
 
+BOX_HEAD_NORM_KEY = "MODEL.ROI_BOX_HEAD.NORM"
+BOX_HEAD_NORMS = ("", "GN")
+
+
+class _HeadConvP(nn.Module):
+    """`weight` (c2_msra_fill), `bias` (zeros; absent with a norm, D2 Conv2d(bias=not norm)) and the `norm` child of one 3x3 conv
+    of the box head, registered in D2's order: weight, bias, norm.weight, norm.bias."""
+
+    def __init__(self, cin, cout, norm):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin, 3, 3))
+        nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
+        if norm:
+            from .backbone import _GroupNormParams      # (solver.norm_parameter_names finds it: SOLVER.WEIGHT_DECAY_NORM applies)
+            self.norm = _GroupNormParams(cout)
+        else:
+            self.bias = nn.Parameter(torch.zeros(cout))
+
+
 @ROI_BOX_HEAD_REGISTRY.register()
 class FastRCNNConvFCHead(nn.Module):
-    """flatten -> fc1 + ReLU -> fc2 + ReLU (D2 FastRCNNConvFCHead), c2_xavier_fill init."""
+    """[conv3x3 -> norm -> ReLU] x NUM_CONV -> flatten -> [fc + ReLU] x NUM_FC: D2 0.5's FastRCNNConvFCHead
+    restated literally -- D2 is not installed here, so parity is by restatement (tests/box_head_ref.py), as for TTA and COCOeval.
+
+    conv{k}: 3x3, stride 1, padding 1, to CONV_DIM channels, bias = not NORM, norm child `conv{k}.norm`, c2_msra_fill init, bias 0;
+    NORM "" or "GN" (GroupNorm(32, CONV_DIM), eps 1e-5, weight 1, bias 0).  fc{k}: c2_xavier_fill init.  Convs come before fcs in
+    the state dict (D2's optimiser numbering).  With NUM_FC == 0 the output stays (R, CONV_DIM, P, P) and `output_size` is its
+    element count.
+
+    The conv layers run on the ROI mosaic (ops.roi_mosaic_*, csrc/roi_mosaic.hip): ROIs packed 64 to a 64 x 64 canvas at P = 7,
+    ops.conv3x3 on the canvases, gutters re-zeroed by the mask (no norm) or by the mosaic GroupNorm.  NUM_CONV == 0 is the fc-only
+    head, launch for launch what it was."""
 
     def __init__(self, cfg, input_shape):
         super().__init__()
         H = cfg.MODEL.ROI_BOX_HEAD
-        assert H.NUM_CONV == 0, "conv layers in the box head are not on the hot path"
-        dim = input_shape.channels * input_shape.height * input_shape.width
-        self.num_fc = H.NUM_FC
+        self.num_conv, self.num_fc = int(H.NUM_CONV), H.NUM_FC
+        self.norm = "" if H.NORM is None else H.NORM
+        if self.norm not in BOX_HEAD_NORMS:
+            raise ValueError(f"{BOX_HEAD_NORM_KEY}={H.NORM!r} is not implemented: accepted values are "
+                             f"{', '.join(repr(v) for v in BOX_HEAD_NORMS)} (BN and SyncBN need running statistics this build does "
+                             "not have)")
+        channels, self.pooled = input_shape.channels, int(input_shape.height)
+        if self.num_conv > 0:
+            from .backbone import GN_GROUPS
+            if input_shape.height != input_shape.width:
+                raise ValueError(f"MODEL.ROI_BOX_HEAD.NUM_CONV={self.num_conv}: the ROI mosaic takes square pooled maps, got "
+                                 f"{input_shape.height} x {input_shape.width}")
+            if self.norm and H.CONV_DIM % GN_GROUPS:
+                raise ValueError(f"{BOX_HEAD_NORM_KEY}='GN': MODEL.ROI_BOX_HEAD.CONV_DIM={H.CONV_DIM} channels do not divide into "
+                                 f"{GN_GROUPS} groups")
+            cell = (H.CONV_DIM // GN_GROUPS) * (self.pooled + 1) ** 2
+            if self.norm and cell > ops.ROI_MOSAIC_GN_MAX_CELL:
+                raise ValueError(f"{BOX_HEAD_NORM_KEY}='GN': a (ROI, group) cell of CONV_DIM / {GN_GROUPS} x (POOLER_RESOLUTION + 1)^2 = "
+                                 f"{cell} floats exceeds the {ops.ROI_MOSAIC_GN_MAX_CELL} the mosaic GroupNorm holds in a wave")
+        for k in range(self.num_conv):
+            setattr(self, f"conv{k + 1}", _HeadConvP(channels, H.CONV_DIM, self.norm))
+            channels = H.CONV_DIM
+        self.conv_dim = channels
+        dim = channels * input_shape.height * input_shape.width
         for k in range(H.NUM_FC):
             fc = _LinearP(dim, H.FC_DIM)
             nn.init.kaiming_uniform_(fc.weight, a=1)
@@ -111,8 +161,38 @@ class FastRCNNConvFCHead(nn.Module):
 
     accepts_deferred_roi_align = True      # forward() takes ROIPooler's DeferredROIAlign (SOLVER.AMP.ENABLED) as well as a tensor
 
+    def _convs(self, x):
+        """(R, C, P, P) -> (R, CONV_DIM, P, P) on the ROI mosaic, at most ops.ROI_MOSAIC_CHUNK ROIs per pack"""
+        total, P = int(x.shape[0]), self.pooled
+        if total == 0:
+            return x.new_zeros((0, self.conv_dim, P, P))
+        outs = []
+        for a in range(0, total, ops.ROI_MOSAIC_CHUNK):
+            xs = x[a:a + ops.ROI_MOSAIC_CHUNK]
+            r = int(xs.shape[0])
+            t = ops.roi_mosaic_pack(xs)
+            for k in range(1, self.num_conv + 1):
+                conv = getattr(self, f"conv{k}")
+                with ops.anomaly_scope(f"conv{k}"):
+                    if self.norm:
+                        t = ops.conv3x3(t, conv.weight, ops.zero_bias(conv.weight.shape[0], t.device), False)
+                        with ops.anomaly_scope("norm"):
+                            t = ops.roi_mosaic_gn_relu(t, conv.norm.weight, conv.norm.bias, r, P, conv.norm.num_groups, conv.norm.eps)
+                    else:
+                        t = ops.conv3x3(t, conv.weight, conv.bias, True)
+                        if k < self.num_conv:       # (the last layer's gutters are never read: unpack takes the data pixels, and its
+                            t = ops.roi_mosaic_mask(t, r, P)        # backward, pack, writes the zeros of dy itself)
+            outs.append(ops.roi_mosaic_unpack(t, r, P))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
     def forward(self, x):
         first = 0
+        if self.num_conv > 0:
+            if isinstance(x, DeferredROIAlign):
+                x = x.materialize()
+            x = self._convs(x)
+            if self.num_fc == 0:
+                return x
         if isinstance(x, DeferredROIAlign):
             from .. import p8
             if self.num_fc and self.fc1.weight.shape[1] >= p8.LINEAR_MIN_K:
@@ -194,6 +274,8 @@ class GuassianFastRCNNOutputLayers(nn.Module):
     nms_by_class: Optional[bool] = None     # inference(): None = by size (select_nms_by_class), True / False force a path
 
     def forward(self, x):
+        if x.dim() > 2:         # a box head that ends in a conv layer (NUM_FC 0): D2's FastRCNNOutputLayers flattens too
+            x = x.flatten(1)
         with ops.anomaly_scope("cls_score"):
             scores = ops.linear(x, self.cls_score.weight, self.cls_score.bias, False)
         with ops.anomaly_scope("bbox_pred"):

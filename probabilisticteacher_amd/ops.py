@@ -875,6 +875,190 @@ def group_norm_relu(z, gamma, beta, groups: int = 32, eps: float = 1e-5, relu: b
     return _GroupNormReLU.apply(z, gamma, beta, int(groups), float(eps), bool(relu))
 
 
+# ============================================================================ ROI mosaic (MODEL.ROI_BOX_HEAD.NUM_CONV > 0)
+# Pooled ROIs (R, C, P, P) packed into canvases (ceil(R / gx^2), C, S, S) -- cell pitch p = P + 1, gx = max(1, 64 // p) cells a side,
+# S = gx * p -- so that conv3x3 sees ordinary maps (csrc/roi_mosaic.hip).  Invariant: gutters (row / column P of a cell) and the
+# cells past R are exactly 0.0 in every tensor a convolution reads (x in forward, dz in backward).
+ROI_MOSAIC_CHUNK = 8192     # ROIs per pack: 128 canvases of 64 x 64, far inside every conv entry's 32-bit offsets and grid bounds
+
+
+def roi_mosaic_geometry(r: int, pooled: int) -> Tuple[int, int, int, int]:
+    """(p, gx, S, canvases) of r ROIs pooled to `pooled` x `pooled`"""
+    p = int(pooled) + 1
+    gx = max(1, 64 // p)
+    return p, gx, gx * p, -(-int(r) // (gx * gx))
+
+
+ROI_MOSAIC_GN_MAX_CELL = 2048   # PTMI_ROI_MOSAIC_GN_MAX_CELL, for code that must not load the library (model construction)
+
+
+def roi_mosaic_gn_max_cell() -> int:
+    """PTMI_ROI_MOSAIC_GN_MAX_CELL: floats of a (ROI, group) cell, (C / G) * (P + 1)^2, the mosaic GroupNorm holds in a wave"""
+    return int(_lib.load().ptmi_roi_mosaic_gn_max_cell())
+
+
+def _mosaic_bytes(r: int, c: int, pooled: int, maps: int) -> float:
+    _, _, s, ncv = roi_mosaic_geometry(r, pooled)
+    return 4.0 * maps * ncv * c * s * s
+
+
+def _mosaic_canvas(canvas, r: int, pooled: int, name: str):
+    _, _, s, ncv = roi_mosaic_geometry(r, pooled)
+    canvas = _chk(canvas.contiguous(), name=name)
+    if canvas.dim() != 4 or canvas.shape[0] != ncv or tuple(canvas.shape[2:]) != (s, s):
+        raise ValueError(f"{name}: expected ({ncv}, C, {s}, {s}) canvases for {r} ROIs of {pooled} x {pooled}, got {tuple(canvas.shape)}")
+    return canvas
+
+
+def _mosaic_pack(x):
+    x = _chk(x.contiguous(), name="roi mosaic input")
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise ValueError(f"roi_mosaic_pack: expected (R, C, P, P) pooled ROIs, got {tuple(x.shape)}")
+    r, c, pooled = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+    _, _, s, ncv = roi_mosaic_geometry(r, pooled)
+    canvas = torch.empty((ncv, c, s, s), dtype=F32, device=x.device)
+    with _prof("roi_mosaic_pack", 0.0, 4.0 * x.numel() + _mosaic_bytes(r, c, pooled, 1)):
+        _lib.call("ptmi_roi_mosaic_pack", _ptr(x), _ptr(canvas), r, c, pooled, _stream())
+    return canvas
+
+
+def _mosaic_unpack(canvas, r: int, pooled: int):
+    canvas = _mosaic_canvas(canvas, r, pooled, "roi mosaic canvas")
+    c = int(canvas.shape[1])
+    x = torch.empty((r, c, pooled, pooled), dtype=F32, device=canvas.device)
+    with _prof("roi_mosaic_unpack", 0.0, 4.0 * x.numel() + _mosaic_bytes(r, c, pooled, 1)):
+        _lib.call("ptmi_roi_mosaic_unpack", _ptr(canvas), _ptr(x), r, c, pooled, _stream())
+    return x
+
+
+def _mosaic_mask(canvas, r: int, pooled: int):
+    canvas = _mosaic_canvas(canvas, r, pooled, "roi mosaic canvas")
+    out = torch.empty_like(canvas)
+    with _prof("roi_mosaic_mask", 0.0, _mosaic_bytes(r, int(canvas.shape[1]), pooled, 2)):
+        _lib.call("ptmi_roi_mosaic_mask", _ptr(canvas), _ptr(out), r, int(canvas.shape[1]), pooled, _stream())
+    return out
+
+
+class _RoiMosaicPack(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.meta = (int(x.shape[0]), int(x.shape[2]))
+        return _mosaic_pack(x)
+
+    @staticmethod
+    def backward(ctx, dcanvas):
+        return _mosaic_unpack(dcanvas, *ctx.meta)
+
+
+class _RoiMosaicUnpack(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, canvas, r, pooled):
+        return _mosaic_unpack(canvas, r, pooled)
+
+    @staticmethod
+    def backward(ctx, dx):
+        return _mosaic_pack(dx), None, None         # (writes the zeros of gutters and empty cells)
+
+
+class _RoiMosaicMask(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, canvas, r, pooled):
+        ctx.meta = (r, pooled)
+        return _mosaic_mask(canvas, r, pooled)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _mosaic_mask(dout, *ctx.meta), None, None
+
+
+def roi_mosaic_pack(x):
+    """(R, C, P, P) pooled ROIs -> (ceil(R / gx^2), C, S, S) canvases, gutters and empty cells 0.0; backward: roi_mosaic_unpack"""
+    _no_native_bf16("ops.roi_mosaic_pack")
+    return _RoiMosaicPack.apply(x)
+
+
+def roi_mosaic_unpack(canvas, r: int, pooled: int):
+    """the data pixels of the canvases -> (r, C, pooled, pooled); backward: roi_mosaic_pack"""
+    _no_native_bf16("ops.roi_mosaic_unpack")
+    return _RoiMosaicUnpack.apply(canvas, int(r), int(pooled))
+
+
+def roi_mosaic_mask(canvas, r: int, pooled: int):
+    """a copy of the canvases with gutters and empty cells zeroed (the input -- a convolution's saved output -- is not written);
+    its own backward"""
+    _no_native_bf16("ops.roi_mosaic_mask")
+    return _RoiMosaicMask.apply(canvas, int(r), int(pooled))
+
+
+def _mosaic_gn_ws(r: int, c: int, pooled: int, groups: int, device) -> torch.Tensor:
+    nbytes = int(_lib.load().ptmi_roi_mosaic_gn_ws_bytes(r, c, pooled, groups))
+    if nbytes < 0:
+        raise _lib.PtmiError(f"ptmi_roi_mosaic_gn_ws_bytes failed: {_lib.load().ptmi_last_error().decode()}")
+    return _ws("roi_mosaic_gn", nbytes, device)
+
+
+class _RoiMosaicGNReLU(torch.autograd.Function):
+    """relu(GroupNorm(groups, C)(z)) per ROI over the data pixels of canvases; y and dz get 0.0 on gutters and empty cells.  Saves
+    z, y and the (ROI, group) statistics; backward recomputes xhat from z."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, r, pooled, groups, eps):
+        z = _mosaic_canvas(z, r, pooled, "roi mosaic group norm input")
+        gamma, beta = _chk(gamma.contiguous(), name="group norm weight"), _chk(beta.contiguous(), name="group norm bias")
+        c = int(z.shape[1])
+        if groups <= 0 or c % groups:
+            raise ValueError(f"roi_mosaic_gn_relu: {c} channels do not divide into {groups} groups")
+        if gamma.numel() != c or beta.numel() != c:
+            raise ValueError(f"roi_mosaic_gn_relu: weight / bias of {gamma.numel()} / {beta.numel()} elements for {c} channels")
+        y = torch.empty_like(z)
+        stats = torch.empty((r * groups, 2), dtype=F32, device=z.device)
+        with _prof("roi_mosaic_gn_fwd", 0.0, _mosaic_bytes(r, c, pooled, 2)):
+            _lib.call("ptmi_roi_mosaic_gn_relu_fwd", _ptr(z), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(stats), r, c, pooled, groups,
+                      float(eps), _stream())
+        ctx.meta = (r, pooled, groups)
+        ctx.save_for_backward(z, y, gamma, stats)
+        if _ANOMALY is not None:
+            _anomaly_fwd(ctx, "roi_mosaic_gn_relu", (("y", y),))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, y, gamma, stats = ctx.saved_tensors
+        r, pooled, groups = ctx.meta
+        dy = _chk(dy.contiguous(), name="roi mosaic group norm grad")
+        c = int(z.shape[1])
+        dz = torch.empty_like(z)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+        if r == 0:
+            dgamma.zero_(), dbeta.zero_()
+        with _prof("roi_mosaic_gn_bwd", 0.0, _mosaic_bytes(r, c, pooled, 7)):       # dy, y, z twice (dgamma / dbeta, dz), dz once
+            _lib.call("ptmi_roi_mosaic_gn_relu_bwd", _ptr(dy), _ptr(y), _ptr(z), _ptr(gamma), _ptr(stats), _ptr(dz), _ptr(dgamma),
+                      _ptr(dbeta), r, c, pooled, groups, _ptr(_mosaic_gn_ws(r, c, pooled, groups, z.device)), _stream())
+        if _ANOMALY is not None:
+            _anomaly_bwd(ctx, "roi_mosaic_gn_relu", (("dgamma", dgamma), ("dbeta", dbeta), ("dz", dz)))
+        return dz, dgamma, dbeta, None, None, None, None
+
+
+def roi_mosaic_gn_relu(z, gamma, beta, r: int, pooled: int, groups: int = 32, eps: float = 1e-5):
+    """relu(group_norm(.)) of each of the r ROIs on (ceil(r / gx^2), C, S, S) canvases, statistics over the ROI's data pixels; the
+    gutters and empty cells of the result (and of the input gradient) are 0.0 whatever z holds there"""
+    _no_native_bf16("ops.roi_mosaic_gn_relu")
+    return _RoiMosaicGNReLU.apply(z, gamma, beta, int(r), int(pooled), int(groups), float(eps))
+
+
+_ZERO_BIAS = {}
+
+
+def zero_bias(n: int, device) -> torch.Tensor:
+    """a cached all-zero fp32 vector: the bias operand of a convolution that has none (D2 Conv2d(bias=not norm)); not a parameter"""
+    device = torch.device(device)
+    key = (int(n), device.type, device.index)
+    t = _ZERO_BIAS.get(key)
+    if t is None:
+        t = _ZERO_BIAS[key] = torch.zeros(int(n), dtype=F32, device=device)
+    return t
+
+
 # ============================================================================ the 3x3 stack: one block node, one conv node
 class NCHW:
     """The fp32 (N, C, H, W) storage layout of the 3x3 stack, as _ConvBlock / _Conv / frozen_block see one (p8.P8 is the bf16 one):

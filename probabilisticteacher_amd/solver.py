@@ -71,7 +71,7 @@ def weight_decay_norm(cfg) -> float:
 def norm_parameter_names(model) -> set:
     """Names (as `model.named_parameters()` gives them) of the parameters D2's get_default_optimizer_params treats as norm
     parameters: those that belong to a norm module directly.  Here the norm modules are the `norm` children of the backbone's
-    convolutions (modeling/backbone.py: _GroupNormParams)."""
+    and the box head's convolutions (modeling/backbone.py: _GroupNormParams)."""
     from .modeling.backbone import _GroupNormParams
     names = set()
     for mod_name, mod in model.named_modules():
